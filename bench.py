@@ -1,6 +1,17 @@
 """Headline benchmark: denoised spectra/s of the fused RRCDNet forward on MI355X (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--arch RRCDNet] [--dtype f16] [--batch B]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set up (weights, on-device inputs,
+packed blob), W warm-up steps, K timed steps, the untimed finiteness check and evaluation metrics of
+the last step's outputs, and the JSON line (`value`, `ms_per_step`, `roofline`, `metrics_mean`).
+`--dump-outputs DIR` also writes what the last timed step computed (DIR/y.npy, see dump_outputs).
+`--full` adds every other leg, each as before: the other engine dtypes and the trained-weights
+timing (`variants`, `trained_weights`), the batch-1 evaluate loop (`batch1`), the simulate -> forward
+-> metrics pipeline (`pipeline`), the config-3 sustained window (`sustained`), BASELINE.json configs
+2/4/5 (`configs`) and the CPU baseline (`cpu_baseline`); the --no-* switches and their size options
+select among those legs and mean nothing without --full (the keys are then null / absent).
 
 The headline dtype is 'f16', the engine's fastest mode within the north-star 16-bit tolerance
 (2e-2 max-abs): on RRCDNet that is RDN_F16MIX -- one v_mfma_f32_16x16x32_f16 per product (the bf16
@@ -9,7 +20,7 @@ the last five right-branch layers with the block-scaled e4m3 correction (DESIGN.
 profiles/r04/parity_table.md).
 The f16 + e4m3-correction mode (f16f8, ~15 significant bits), split bf16 (bf16x3), single-rounding
 bf16 ('bf16-unsafe', NOT within 2e-2 on trained RRCDNet) and fp32 (compensated, within 1e-5) are
-timed as "variants" in the same line.
+timed as "variants" in the same line under --full.
 
 One step = one forward of the fused network over a batch of B synthetic spectra per GPU (L = 10000),
 generated on-device by the engine's simulator BEFORE the timed region (inputs resident in HBM).
@@ -249,6 +260,30 @@ def traffic_per_spectrum(arch, dtype):
         return (rec["bytes_per_spectrum"], rec["source"]) if rec else (None, None)
     except (OSError, ValueError, KeyError):
         return None, None
+
+
+DUMP_BYTES = 48 * 10 ** 6     # --dump-outputs budget over all ranks (fp32 rows; stays below 64 MB)
+
+
+def dump_rows(B, L, world):
+    """Rows of a (B, L) fp32 output --dump-outputs keeps per rank: all of them if every rank's array
+    fits DUMP_BYTES together, else a fixed sample (numpy default_rng(0), sorted) -- a function of
+    (B, L, world) alone, so two builds run with the same arguments dump the same spectra."""
+    n = DUMP_BYTES // max(1, world) // (4 * L)
+    if n >= B:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(0).choice(B, max(1, n), replace=False))
+
+
+def dump_outputs(dirname, y, world, rank):
+    """--dump-outputs DIR: the denoised spectra the last timed step wrote -- the (B, 1, L) tensor a
+    caller of engine.forward receives -- as float32 DIR/y.npy (rank r > 0 of an N-GPU run:
+    DIR/y_rank<r>.npy), rows dump_rows(B, L, world) of it (every rank simulates its own spectra)."""
+    B, _, L = y.shape
+    rows = dump_rows(B, L, world)
+    arr = y.view(B, L)[torch.from_numpy(rows).to(y.device)].cpu().numpy().astype(np.float32, copy=False)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "y.npy" if rank == 0 else f"y_rank{rank}.npy"), arr)
 
 
 def time_forward(engine, arch, dtype, packed, x, y, steps, warmup, stream):
@@ -508,6 +543,12 @@ def main():
     ap.add_argument("--batch", type=int, default=8192, help="spectra per GPU per step")
     ap.add_argument("--L", type=int, default=10000)
     ap.add_argument("--seed", type=int, default=20250410)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/y.npy (float32; a fixed "
+                         "sample of spectra when the whole batch exceeds the dump budget)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (variants, trained weights, batch-1, pipeline, sustained, "
+                         "configs 2/4/5, CPU baseline); the options below select among them")
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="per CPU-baseline variant (3 variants)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-variants", action="store_true", help="skip timing the other engine dtypes")
@@ -605,14 +646,18 @@ def main():
     # the timed launches ran unchecked (check=False); a failed CBAM hand-off would show as NaN here
     if not bool(torch.isfinite(y).all()):
         raise RuntimeError("non-finite outputs in the timed forward")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, world, rank)      # before any other leg reuses y
     # evaluation metrics of the last step, all-reduced across ranks (RCCL over xGMI) — untimed
     _, sums = engine.metrics(y.view(B, L), clean)
     if distributed:
         all_reduce(sums)
     sums = sums.cpu().tolist()
 
+    # everything below the headline runs under --full only
+    full = args.full
     variants = {}
-    if not args.no_variants:
+    if full and not args.no_variants:
         progress("variants")
         for dt in ("f16", "f16-plain", "f16f8", "bf16x3", "bf16-unsafe", "fp32"):
             if dt == args.dtype:
@@ -627,7 +672,7 @@ def main():
     # the headline kernel on the trained golden fixture weights (the clock the chip holds depends on
     # the operands: MI355X_MICROARCH.md DVFS give-back), beside the random-init `value`
     trained = None
-    if not args.no_variants:
+    if full and not args.no_variants:
         mt, tsrc = _model(R, args.arch, args.dtype, dev)
         ms = time_forward(engine, args.arch, mt.engine_code, mt.packed_weights(dev), x, y, max(3, args.steps // 4), 1, stream)
         trained = {"spectra_per_s_per_gpu": B / (ms * 1e-3), "kernel_ms": ms, "batch": B, "weights": tsrc,
@@ -635,26 +680,26 @@ def main():
         del mt
 
     batch1 = None
-    if not args.no_batch1 and rank == 0:
+    if full and not args.no_batch1 and rank == 0:
         progress("batch-1 latency")
         batch1 = batch1_latency(model, code, args.arch, L, dev)
 
     pipeline = None
-    if not args.no_pipeline:
+    if full and not args.no_pipeline:
         progress("pipeline")
         # each rank's pipeline block of (PIPELINE_STEPS + 1)*B indices after every rank's headline batch
         pipeline = time_pipeline(engine, args.arch, code, packed, args.seed, blocks["pipeline"][0], B, L,
                                  PIPELINE_STEPS, stream, dev)
 
     sustained = None
-    if args.sustained_seconds > 0:
+    if full and args.sustained_seconds > 0:
         progress(f"sustained: >= {args.sustained_seconds:g} s and >= {args.sustained_spectra} spectra")
         sustained = time_sustained(engine, args.arch, code, packed, args.seed, blocks["sustained_first"], B, L,
                                    args.sustained_seconds, args.sustained_spectra, stream, dev,
                                    flops_per_spectrum(args.arch, L), PEAK_TFLOPS[args.dtype])
 
     configs = None
-    if not args.no_configs:
+    if full and not args.no_configs:
         configs = config_keys(R, engine, args, dev, stream, world, rank, blocks)
 
     if rank == 0:
@@ -687,7 +732,7 @@ def main():
             "batch1": batch1,
             "metrics_mean": {k: sums[i] / sums[4] for i, k in enumerate(["MSE", "SSIM", "Smoothness", "Peak2Peak"])},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(args.arch, L, args.cpu_seconds)
         print(json.dumps(rec), flush=True)
     if distributed:

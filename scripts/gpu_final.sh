@@ -10,12 +10,12 @@ OUT=${OUT:-gpurun_out/final}
 mkdir -p $OUT
 STAGES=${STAGES:-bench kt pmc}
 if [[ " $STAGES " == *" bench "* ]]; then
-  timeout -k 10 600 python -u bench.py > $OUT/bench.log 2>&1
+  timeout -k 10 600 python -u bench.py --full > $OUT/bench.log 2>&1
   rc=$?; echo "bench rc=$rc"; tail -1 $OUT/bench.log | cut -c1-400; if [ $rc -ne 0 ]; then exit $rc; fi
   grep "^{" $OUT/bench.log | tail -1 > $OUT/bench.json
 fi
 if [[ " $STAGES " == *" kt "* ]]; then
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 bench.py --no-cpu-baseline --no-configs --sustained-seconds 0 > $OUT/kt_bench.log 2>&1
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 bench.py --full --no-cpu-baseline --no-configs --sustained-seconds 0 > $OUT/kt_bench.log 2>&1
   rc=$?; echo "kt rc=$rc"; tail -1 $OUT/kt_bench.log | cut -c1-300; if [ $rc -ne 0 ]; then exit $rc; fi
   grep "^{" $OUT/kt_bench.log | tail -1 > $OUT/kt_bench.json
 fi

@@ -14,7 +14,7 @@ if [[ " $STAGES " == *" parity "* ]]; then
   rc=$?; echo "parity rc=$rc"; if [ $rc -ne 0 ]; then tail -5 $OUT/parity.log; exit $rc; fi
 fi
 if [[ " $STAGES " == *" kt "* ]]; then
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 bench.py > $OUT/kt_bench.log 2>&1
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 bench.py --full > $OUT/kt_bench.log 2>&1
   rc=$?; echo "kt rc=$rc"; tail -1 $OUT/kt_bench.log | cut -c1-300; if [ $rc -ne 0 ]; then exit $rc; fi
 fi
 # PMC passes: the timed launches only (batch 8192; no batch-1 loop, no variants, no pipeline), so

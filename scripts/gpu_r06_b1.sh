@@ -11,5 +11,5 @@ for a in ADSDN APIDN RRCDNet DSDN; do
   B1_ARCH=$a timeout -k 10 300 python -u tools/batch1_profile.py > $OUT/batch1_$a.log 2>&1
   rc=$?; echo "$a: $(grep -m1 module $OUT/batch1_$a.log)"; if [ $rc -ne 0 ]; then tail -5 $OUT/batch1_$a.log; exit $rc; fi
 done
-timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; python3 -c "import json;d=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1]);print(d['value'],d['roofline']['frac'],d.get('batch1'))"; exit $rc

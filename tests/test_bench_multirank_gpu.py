@@ -19,7 +19,7 @@ def test_bench_two_ranks_gloo():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29531", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64", "--L", "2000",
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64", "--L", "2000", "--full",
            "--dist-backend", "gloo", "--no-cpu-baseline", "--no-variants", "--no-batch1", "--no-pipeline",
            "--config4-batch", "16", "--config4-chunks", "2", "--config4-archs", "RRCDNet,DSDN"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
@@ -87,7 +87,7 @@ def test_rccl_leg_runs_one_rank(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", "29545", os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--L", "2000",
+           "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--L", "2000", "--full",
            "--no-cpu-baseline", "--no-variants", "--no-batch1", "--config4-batch", "16", "--config4-chunks", "2",
            "--config2-n", "64", "--config2-batch", "32"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)

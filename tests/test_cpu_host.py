@@ -236,6 +236,18 @@ def test_bench_index_blocks_disjoint(world):
     assert ranges[0][0] == 0
 
 
+@pytest.mark.parametrize("world", [1, 2, 8])
+def test_bench_dump_rows_fixed_sample_within_budget(world):
+    """--dump-outputs keeps a fixed sample of the default (8192, 10000) batch: the same sorted, distinct
+    rows on every call, all ranks' float32 arrays together under 64 MB; a batch that fits is kept whole."""
+    bench = _bench_module()
+    rows = bench.dump_rows(8192, 10000, world)
+    np.testing.assert_array_equal(rows, bench.dump_rows(8192, 10000, world))
+    assert rows.ndim == 1 and len(rows) >= 1 and (np.diff(rows) > 0).all() and 0 <= rows[0] and rows[-1] < 8192
+    assert world * (len(rows) * 10000 * 4 + 128) <= 64 * 10 ** 6
+    np.testing.assert_array_equal(bench.dump_rows(64, 2000, world), np.arange(64))
+
+
 def test_bench_gpus_flag_launches_ranks(monkeypatch):
     """`python bench.py --gpus N` without torchrun starts N ranks under torch.distributed.run (before any
     GPU call), forwarding its arguments; with WORLD_SIZE set (a launched rank) it does not re-launch."""

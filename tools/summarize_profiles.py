@@ -3,8 +3,8 @@
     python tools/summarize_profiles.py gpurun_out/prof profiles/r01       (scripts/gpu_profile.sh)
     python tools/summarize_profiles.py gpurun_out/final profiles/r03      (scripts/gpu_final.sh)
 
-Writes <dst>/rocprof/kernel_stats_bench.csv (rocprofv3 --kernel-trace --stats of the default
-`python bench.py`), <dst>/rocprof/kernel_stats_by_grid.csv (the same trace per kernel AND grid size:
+Writes <dst>/rocprof/kernel_stats_bench.csv (rocprofv3 --kernel-trace --stats of
+`python bench.py --full`), <dst>/rocprof/kernel_stats_by_grid.csv (the same trace per kernel AND grid size:
 the headline batch separated from the batch-1 latency launches), <dst>/rocprof/pmc_summary.json (per-dispatch averages of every PMC counter for
 the fused RRCDNet kernels), <dst>/parity_table.md, and profiles/traffic.json: HBM bytes per
 spectrum of each dtype's kernel = (2 x FETCH_SIZE + WRITE_SIZE) KiB per dispatch / batch — FETCH_SIZE
