@@ -278,12 +278,15 @@ static int forward_impl(const char* who, int arch, int dtype, const void* packed
     unsigned* status = status_word(dtype) && ws && ws_bytes >= RANGE_WS_BYTES ? (unsigned*)ws : nullptr;
     const bool shrt = dtype != RDN_BF16 && short_tiles(arch, n, L, s);
     const bool walk = dtype != RDN_BF16 && !shrt && walk_tiles(arch, dtype, n, L, s);
+    // the epilogue's direct path (spectra too long for the LDS, metrics.hpp walk_metrics_t) addresses y
+    // with 32-bit byte counts: from L = 2^29 on the walk runs without it (kmo) and the metrics kernel follows
+    const rdn::met::MetricOut* kmo = L < ((int64_t)1 << 29) ? mo : nullptr;
     if (dtype == RDN_BF16) e = rdn::launch_fused16(arch, blob, x, y, n, (int)L, status, s);
-    else if (dtype == RDN_F16 && walk) e = rdn::launch_fused16_f16_walk(arch, blob, x, y, n, (int)L, status, mo, s), done = true;
+    else if (dtype == RDN_F16 && walk) e = rdn::launch_fused16_f16_walk(arch, blob, x, y, n, (int)L, status, kmo, s), done = kmo != nullptr;
     else if (dtype == RDN_F16)
       e = shrt ? rdn::launch_fused16_f16_small(arch, blob, x, y, n, (int)L, status, s)
                : rdn::launch_fused16_f16(arch, blob, x, y, n, (int)L, status, s);
-    else if (dtype == RDN_F16MIX && walk) e = rdn::launch_fused_inplace_walk(blob, x, y, n, (int)L, status, mo, s), done = true;
+    else if (dtype == RDN_F16MIX && walk) e = rdn::launch_fused_inplace_walk(blob, x, y, n, (int)L, status, kmo, s), done = kmo != nullptr;
     else if (dtype == RDN_F16MIX && shrt) e = rdn::launch_fused_inplace_short(blob, x, y, n, (int)L, status, s);
     else e = rdn::launch_fused_inplace(arch, dtype, blob, x, y, n, (int)L, status, s);
   }

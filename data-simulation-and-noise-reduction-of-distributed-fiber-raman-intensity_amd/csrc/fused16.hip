@@ -290,7 +290,11 @@ __device__ __forceinline__ void dsdn_tile(Tile& tl, float* y, int t, int ntiles,
   lds_barrier();
 }
 
-#define H16_WALK_KERNEL(name, SHIFT, C0)                                                                   \
+// the LDS the walk kernels' metric epilogue may index: what the launcher below gives them (576-row
+// tiles: 2 * 580 * 128 + 88 * 128 = 159744 B, less than a CU's 163840)
+constexpr int WALK_MET_LDS = (int)LDS_BYTES;
+
+#define H16_WALK_KERNEL(name, SHIFT, C0)                                                               \
   __global__ __launch_bounds__(THREADS) void name##_walk(const uint8_t* __restrict__ blob,                 \
                                                          const float* __restrict__ x, float* __restrict__ y, \
                                                          int L, int ntiles, unsigned* __restrict__ status, \
@@ -309,7 +313,8 @@ __device__ __forceinline__ void dsdn_tile(Tile& tl, float* y, int t, int ntiles,
       else name##_tile<false>(tl, y, t, ntiles, F0, F1, xs);                                               \
       tl.first = false;                                                                                    \
     }                                                                                                      \
-    if (mo.clean) met::walk_metrics(y, L, n, lds, mo);  /* the metric epilogue: y read back from L2 */    \
+    /* the metric epilogue: y read back from L2, staged into this kernel's WALK_MET_LDS bytes of LDS */    \
+    if (mo.clean) met::walk_metrics<WALK_MET_LDS>(y, L, n, lds, mo);                                       \
   }
 
 H16_WALK_KERNEL(denoisecnn, DENOISECNN_SHIFT, 0)
@@ -335,12 +340,14 @@ hipError_t H16_LAUNCH(int arch, const uint8_t* blob, const float* x, float* y, i
     case DSDN: k = H16_NS::dsdn_walk; shift = H16_NS::DSDN_SHIFT; break;
     default: return hipErrorInvalidValue;
   }
-  const hipError_t e = ensure_dynamic_lds((const void*)k, H16_ATTR_SLOT0 + arch, (int)H16_NS::LDS_BYTES, stream_device(stream));
+  constexpr uint32_t lds_bytes = H16_NS::LDS_BYTES;
+  static_assert(lds_bytes == (uint32_t)H16_NS::WALK_MET_LDS, "launched with the LDS the metric epilogue was compiled for");
+  const hipError_t e = ensure_dynamic_lds((const void*)k, H16_ATTR_SLOT0 + arch, (int)lds_bytes, stream_device(stream));
   if (e != hipSuccess) return e;
   const int ntiles = (int)(((int64_t)L + shift + H16_NS::WT - 1) / H16_NS::WT);
   for (int64_t n0 = 0; n0 < n; n0 += 0x7fffffff) {
     const int64_t nn = n - n0 < 0x7fffffff ? n - n0 : 0x7fffffff;
-    hipLaunchKernelGGL(k, dim3((unsigned)nn), dim3(H16_NS::THREADS), H16_NS::LDS_BYTES, stream, blob, x + n0 * L,
+    hipLaunchKernelGGL(k, dim3((unsigned)nn), dim3(H16_NS::THREADS), lds_bytes, stream, blob, x + n0 * L,
                        y + n0 * L, L, ntiles, status, met::chunk(mo, n0, L));
   }
   return hipGetLastError();

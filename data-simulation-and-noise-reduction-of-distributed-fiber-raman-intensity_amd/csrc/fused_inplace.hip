@@ -305,6 +305,10 @@ __global__ __launch_bounds__(THREADS) void rrcdnet_hybrid(const uint8_t* __restr
   rrcdnet_hybrid_tile<TAIL>(lds, blob, x, y, L, T, tiles, status, __builtin_amdgcn_workgroup_id_x());
 }
 
+// Dynamic LDS of rrcdnet_hybrid_walk (the whole LDS of a CU): the carry slots and the vote words are
+// laid out against it, the launcher gives it, and the metric epilogue is compiled for it
+constexpr int HYB_WALK_LDS = 163840;
+
 #include "rrcdnet_hybrid_walk.hpp"
 
 // Whether any input of spectrum xs lies outside [lo, hi] (workgroup-uniform; vote words at the end of
@@ -317,7 +321,7 @@ __device__ __forceinline__ bool spectrum_outside(char* lds, const float* xs, int
       out = out || v < lo || v > hi;
     }
   }
-  unsigned* vote = (unsigned*)(lds + 163840) - THREADS / 64;
+  unsigned* vote = (unsigned*)(lds + HYB_WALK_LDS) - THREADS / 64;
   const bool wave_out = __builtin_amdgcn_ballot_w64(out) != 0;
   if ((__builtin_amdgcn_workitem_id_x() & 63) == 0) vote[__builtin_amdgcn_workitem_id_x() >> 6] = wave_out ? 1u : 0u;
   __syncthreads();
@@ -409,7 +413,7 @@ __global__ __launch_bounds__(THREADS) void rrcdnet_hybrid_walk(const uint8_t* __
     const char* ka = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(ka));
     const HybWalkArgs* a = (const HybWalkArgs*)ka;
-    met::walk_metrics(a->y + (size_t)n * a->L, a->L, n, lds, a->mo);
+    met::walk_metrics<HYB_WALK_LDS>(a->y + (size_t)n * a->L, a->L, n, lds, a->mo);
   }
 }
 
@@ -491,14 +495,16 @@ hipError_t launch_fused_inplace_walk(const uint8_t* blob, const float* x, float*
                                      const met::MetricOut* mo, hipStream_t stream) {
   const bool met = mo && mo->clean;
   const auto k = met ? ip::rrcdnet_hybrid_walk<ip::RRCDNET_F16MIX_TAIL, true> : ip::rrcdnet_hybrid_walk<ip::RRCDNET_F16MIX_TAIL, false>;
+  constexpr uint32_t lds_bytes = ip::TileGeo<5>::LDS;   // the tiled hybrid's 640 rows (a spiked spectrum) fill it
+  static_assert(lds_bytes == (uint32_t)ip::HYB_WALK_LDS, "launched with the LDS the kernel and its metric epilogue were compiled for");
   // attribute slots 93 / 94, host_util.hpp
-  const hipError_t e = ensure_dynamic_lds((const void*)k, met ? 94 : 93, 163840, stream_device(stream));
+  const hipError_t e = ensure_dynamic_lds((const void*)k, met ? 94 : 93, (int)lds_bytes, stream_device(stream));
   if (e != hipSuccess) return e;
   const int H = fused_halo(RRCDNET), T = ip::TileGeo<5>::WB - 2 * H, tiles = (L + T - 1) / T;
   const int ntiles = (int)(((int64_t)L + walk_shift(RRCDNET) + RDN_WALK_ROWS_MIX - 1) / RDN_WALK_ROWS_MIX);
   for (int64_t n0 = 0; n0 < n; n0 += 0x7fffffff) {
     const int64_t nn = n - n0 < 0x7fffffff ? n - n0 : 0x7fffffff;
-    hipLaunchKernelGGL(k, dim3((unsigned)nn), dim3(THREADS), 163840, stream, blob, x + n0 * L, y + n0 * L, L, T, tiles,
+    hipLaunchKernelGGL(k, dim3((unsigned)nn), dim3(THREADS), lds_bytes, stream, blob, x + n0 * L, y + n0 * L, L, T, tiles,
                        ntiles, status, met::chunk(mo, n0, L));
   }
   return hipGetLastError();

@@ -159,6 +159,14 @@ __device__ __forceinline__ void spectrum_metrics(YV yv, const TC* __restrict__ c
 // y and clean are first staged into the LDS with eight loads in flight per thread (one round trip per
 // 4096 values, not one per value), and the metric loops then read the LDS; spectra too long for the
 // LDS read memory directly.  The values are the same either way (the same routine on the same numbers).
+//
+// LDS_BYTES is the dynamic LDS the calling kernel is launched with (a walk kernel's whole allocation
+// is the epilogue's once the walk is done): the reduction scratch (RED_DOUBLES doubles, 384 B), y's
+// row (4 L rounded up to 16 B) and the clean row (4 L or 8 L) are staged iff they fit into it:
+//   rrcdnet_hybrid_walk (RDN_F16MIX), 163840 B: L <= 20432 (fp32 clean), L <= 13620 (fp64 clean);
+//   the fused16 walk kernels (RDN_F16),  159744 B: L <= 19920 (fp32 clean), L <= 13280 (fp64 clean).
+// The direct path addresses y through a buffer descriptor of 4 L bytes with 32-bit offsets: the host
+// (abi.cpp forward_impl) does not fuse the metrics for L >= 2^29.
 template <typename T, class LD>
 __device__ __forceinline__ void stage_row(T* dst, int L, LD ld) {
   const int tid = __builtin_amdgcn_workitem_id_x();
@@ -176,15 +184,16 @@ __device__ __forceinline__ void stage_row(T* dst, int L, LD ld) {
     }
   }
 }
-template <typename TC>
+template <int LDS_BYTES, typename TC>
 __device__ __forceinline__ void walk_metrics_t(const float* y, const TC* cc, int L, int64_t n, char* lds,
                                                const MetricOut& mo) {
   const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, L * 4, 0x00020000);
   const auto yg = [&](int p) { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(yr, 4 * p, 0, 16)); };
   double* red = (double*)lds;
-  constexpr int RED = RED_DOUBLES * 8, LDS_MAX = 163840;
+  constexpr int RED = RED_DOUBLES * 8;
+  static_assert(LDS_BYTES >= RED && LDS_BYTES <= 163840, "the launching kernel's dynamic LDS");
   const int yb = (L * 4 + 15) & ~15;
-  if (RED + yb + (size_t)L * sizeof(TC) <= (size_t)LDS_MAX) {
+  if (RED + yb + (size_t)L * sizeof(TC) <= (size_t)LDS_BYTES) {
     float* ys = (float*)(lds + RED);
     TC* cs = (TC*)(lds + RED + yb);
     stage_row(ys, L, yg);
@@ -195,11 +204,12 @@ __device__ __forceinline__ void walk_metrics_t(const float* y, const TC* cc, int
     spectrum_metrics(yg, cc, L, n, red, mo);
   }
 }
+template <int LDS_BYTES>
 __device__ __forceinline__ void walk_metrics(const float* y, int L, int64_t n, char* lds, const MetricOut& mo) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's y stores are in L2
   __syncthreads();
-  if (mo.clean_f64) walk_metrics_t(y, (const double*)mo.clean + (size_t)n * L, L, n, lds, mo);
-  else walk_metrics_t(y, (const float*)mo.clean + (size_t)n * L, L, n, lds, mo);
+  if (mo.clean_f64) walk_metrics_t<LDS_BYTES>(y, (const double*)mo.clean + (size_t)n * L, L, n, lds, mo);
+  else walk_metrics_t<LDS_BYTES>(y, (const float*)mo.clean + (size_t)n * L, L, n, lds, mo);
   __syncthreads();                                      // the LDS the next use may overwrite
 }
 

@@ -27,7 +27,7 @@ using WG = WalkGeo<WNBK>;
 static_assert(PP::WT == WG::WB && PP::CG == WG::GRD, "one walk tile, two engines");
 constexpr int RIGHT_C0 = walk_shift(RRCDNET) - 16;   // the right stem's extra shift (both heads at 28)
 constexpr int CARRY_BYTES = 9 * 2 * 128 + 6 * 2 * 256 + 52 * 128;   // layers 0-8 | 9-14 | left 15-28
-static_assert(PP::CARRY_OFF + CARRY_BYTES <= 163840 - 64, "carry slots below the vote words");
+static_assert(PP::CARRY_OFF + CARRY_BYTES <= HYB_WALK_LDS - 64, "carry slots below the vote words");
 static_assert(WG::LDS <= PP::CARRY_OFF, "the in-place tile inside the ping-pong buffers");
 
 // layer 9's outputs, split in VGPRs into the in-place tile's planes (rrcdnet_hybrid.hpp H8Stage on the
