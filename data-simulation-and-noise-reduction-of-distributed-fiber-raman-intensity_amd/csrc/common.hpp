@@ -99,21 +99,6 @@ __device__ __forceinline__ void raise_status(unsigned* status, unsigned bit) {
   __hip_atomic_fetch_or(status, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Static issue priority of one half of a 512-thread workgroup (MI355X_MICROARCH.md "Two waves per SIMD"
-// item 4: waves w and w + 4 share a SIMD, and the second-dispatched half loses the VALU / LDS issue
-// arbitration to the first at equal priority).  RDN_SETPRIO = 1: waves 4-7 at priority 1; 2: waves 0-3;
-// 0: none.  Set once at kernel entry, never flipped.
-#ifndef RDN_SETPRIO
-#define RDN_SETPRIO 0
-#endif
-__device__ __forceinline__ void wave_priority() {
-#if RDN_SETPRIO == 1
-  if (__builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() >> 6) >= 4) __builtin_amdgcn_s_setprio(1);
-#elif RDN_SETPRIO == 2
-  if (__builtin_amdgcn_readfirstlane(__builtin_amdgcn_workitem_id_x() >> 6) < 4) __builtin_amdgcn_s_setprio(1);
-#endif
-}
-
 // 16-bit single-rounding layout of fused16.hip (RDN_BF16, non-CBAM networks): the same
 // [m 4][kstep 6][lane 64][8] fragments + bias, but with the K order permuted so that element j of
 // lane quarter q in k-step (t, u) is cin = h16_channel(4u + q, j) — the channel held by element j

@@ -300,7 +300,6 @@ constexpr int WALK_MET_LDS = (int)LDS_BYTES;
                                                          int L, int ntiles, unsigned* __restrict__ status, \
                                                          met::MetricOut mo) {                               \
     extern __shared__ __attribute__((aligned(16))) char lds[];                                             \
-    wave_priority();                                                                                       \
     const int n = __builtin_amdgcn_workgroup_id_x();                                                       \
     Tile tl = init_tile(lds, blob, blob + SMALL_BYTES, x + (size_t)n * L, L, 0);                           \
     tl.status = status;                                                                                    \

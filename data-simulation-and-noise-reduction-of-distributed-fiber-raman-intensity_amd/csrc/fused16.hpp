@@ -98,21 +98,6 @@ constexpr int BIAS_OFF = H16_BIAS_OFF;
 #ifndef RDN_H16_PF
 #define RDN_H16_PF 3
 #endif
-#ifndef RDN_H16_ESPLIT
-#define RDN_H16_ESPLIT 0
-#endif
-#ifndef RDN_PRIO_SWITCH
-// Ping-pong layers: the two waves of a SIMD (w, w + 4: the two channel halves) share its MFMA pipe, and
-// at equal priority the arbiter favours the older wave, so waves 0-3 finish a layer's MFMA stream ~1k
-// cycles before waves 4-7, which then run it alone (one wave per SIMD) up to the barrier
-// (tools/hyb_stamps.py, per-wave layer stamps).  RDN_PRIO_SWITCH = k > 0: waves 4-7 raise their
-// priority when they reach N-tile k of a layer (and drop it at the next layer's start), so that both
-// waves of a SIMD reach the barrier together
-#define RDN_PRIO_SWITCH 0
-#endif
-#ifndef RDN_H16_SGB
-#define RDN_H16_SGB 0
-#endif
 // A tile holding positions outside [0, L) stores its layer outputs unmasked (the MFMA loop is the
 // interior tiles' own) and each wave then zeroes its rows outside [0, L) -- a few stores after the
 // loop, before the barrier (zero_outside; a per-lane range check and select in every epilogue made
@@ -521,9 +506,6 @@ __device__ __forceinline__ void layer(Tile& tl, uint32_t src, uint32_t dst, int 
     cc = carry_load(tl, src, CA);
   }
   const int pos0 = tl.base + CG + rblock(w) * RW;
-#if RDN_PRIO_SWITCH
-  if (h) __builtin_amdgcn_s_setprio(0);
-#endif
 
   // Idle waves of a short last tile: every row of this wave lies at position >= L + 2, beyond the
   // reach (d <= 2) of any row that matters, so it skips the layer's MFMAs and only zeroes its dst
@@ -616,10 +598,6 @@ __device__ __forceinline__ void layer(Tile& tl, uint32_t src, uint32_t dst, int 
   Acc prev;
   constexpr int PF = RDN_H16_PF;       // B fragments in flight ahead of the step that consumes them
   constexpr int K = KS * NT;           // steps (N-tile n, k-step s), k = KS n + s
-  // RDN_H16_ESPLIT = e > 1 (f16 RELU / LINEAR layers): the previous N-tile's rounding and ReLU at step
-  // 1, its ds_write_b128 at step e, so one step no longer carries the whole epilogue (diagnostic A/B)
-  constexpr bool ESPLIT = RDN_H16_ESPLIT > 1 && RDN_H16_F16 && (EPI == RELU || EPI == LINEAR);
-  V pend;
   V B[PF + 1];
 #pragma unroll
   for (int k = 0; k < PF; ++k) B[k] = *(const V*)(tl.lds + ba.at(k / KS, k % KS));
@@ -629,9 +607,6 @@ __device__ __forceinline__ void layer(Tile& tl, uint32_t src, uint32_t dst, int 
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
       const int k = KS * n + s, kp = k + PF;
-#if RDN_PRIO_SWITCH
-      if (n == RDN_PRIO_SWITCH && s == 0 && h) __builtin_amdgcn_s_setprio(1);
-#endif
 #if defined(RDN_ABLATE_NOLDS)
       if (kp < K) { B[kp % (PF + 1)] = B[(k + 1) % (PF + 1)]; asm volatile("" : "+v"(B[kp % (PF + 1)])); }
 #else
@@ -645,31 +620,12 @@ __device__ __forceinline__ void layer(Tile& tl, uint32_t src, uint32_t dst, int 
       if (LST && k == 0) lt[1] = __builtin_amdgcn_s_memtime();
       if (LST && k == K - 1) lt[2] = __builtin_amdgcn_s_memtime();
 #endif
-      if constexpr (ESPLIT) {
-        if (n > 0 && s == 1) {
-          V hv = __builtin_convertvector(__builtin_shufflevector(prev.v[0], prev.v[1], 0, 1, 2, 3, 4, 5, 6, 7), V);
-          if (EPI == RELU) hv = __builtin_elementwise_max(hv, (V)((E)0));
-          pend = hv;
-        }
-        if (n > 0 && s == RDN_H16_ESPLIT) *(V*)(tl.lds + sa + (n - 1) * NR * ROWB) = pend;
-      } else {
-        if (n > 0 && s == 1) epilogue(n - 1, prev);
-      }
+      if (n > 0 && s == 1) epilogue(n - 1, prev);
       if (WALK && n == 1 && s == 0) carry_store(tl, dst, CA, cc, CROW);
 #if !defined(RDN_ABLATE_NOALOAD)
       // the next layer's operands, one buffer load every LDSTEP-th step: the vector-memory traffic
       // of the CU's 8 waves spreads over the layer
       if (has_next && k % LDSTEP == 0 && k / LDSTEP < NLOAD) load_op(tl, next, h, k / LDSTEP, lo, G);
-#endif
-#if RDN_H16_SGB
-      // explicit interleave inside the step (diagnostic A/B): MFMA, VALU, B read, MFMA, VALU, store, load
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, RDN_H16_SGB, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);
-      __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
 #endif
       __builtin_amdgcn_sched_barrier(0);
     }

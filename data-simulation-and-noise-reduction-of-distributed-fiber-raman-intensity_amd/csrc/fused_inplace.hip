@@ -405,7 +405,6 @@ __global__ __launch_bounds__(THREADS) void rrcdnet_hybrid_walk(const uint8_t* __
                                                                int L, int T, int tiles, int ntiles,
                                                                unsigned* __restrict__ status, met::MetricOut mo) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  wave_priority();
   const int n = __builtin_amdgcn_workgroup_id_x();
   hybrid_walk_spectrum<TAIL>(lds, blob, x, y, L, T, tiles, ntiles, status, n);
   if (MET) {

@@ -47,27 +47,6 @@ template <int NBK> struct TileGeo {
 // layer's input, taps r - 2d, r - d, r: nothing is read past the computed rows), no wrap.
 // WB = RDN_WALK_ROWS_MIX computed rows in NBK blocks; when WB = 128 NBK - 64 the last block is half
 // (HALF): its rows are those of the waves of quarters nq = 0, 1, and the waves of quarters 2, 3 skip it.
-#ifndef RDN_HALF_REMAP
-#define RDN_HALF_REMAP 0
-#endif
-#ifndef RDN_TAIL_SWAP
-#define RDN_TAIL_SWAP 0       // A/B: the half block on waves 4-7 instead of 0-3 (inplace.hpp conv)
-#endif
-#ifndef RDN_TAIL_EARLY
-#define RDN_TAIL_EARLY 0      // A/B: next-layer operand loads of the half block's idle waves one block early
-                              // (1: all; 2: the fragments, bias and scales at the last block; 3: k-step 0 only)
-#endif
-#ifndef RDN_STAGE_FIRST
-#define RDN_STAGE_FIRST 0     // A/B (the hybrid walk): layer 9's plane stores before the tail's operand loads
-#endif
-#ifndef RDN_TAIL_SGB
-// A/B: the corrected layers' write-back VALU (e4m3 split of block j-2) interleaved between the last
-// N-tile's MFMAs of the k-step, RDN_TAIL_SGB VALU per MFMA (sched_group_barrier); 0 = off
-#define RDN_TAIL_SGB 0
-#endif
-#ifndef RDN_TAIL_STAG
-#define RDN_TAIL_STAG 0       // diagnostic A/B: the in-place write-back of waves 4-7 one k-step late
-#endif
 template <int NBK> struct WalkGeo {
   static constexpr int WB = RDN_WALK_ROWS_MIX;
   static constexpr bool HALF = WB == 128 * NBK - 64;
@@ -666,19 +645,10 @@ __device__ __forceinline__ uint32_t load_scale(const uint8_t* wl, int m) {
   return MODE == MODE_H8 ? ((const uint32_t*)(wl + H8_SCALE_OFF))[m * 64 + (__builtin_amdgcn_workitem_id_x() & 63)] : 0u;
 }
 
-template <int MODE, bool SOUTER = false>
+template <int MODE>
 __device__ __forceinline__ void load_layer_a(const Tile& tl, int layer, LayerA<MODE>& a) {
   const int tid = opaque_tid(), mp = (tid >> 6) & 1, lane = tid & 63;
   const uint8_t* wl = tl.big + (size_t)layer * LayerBytes<MODE>::BYTES;
-  if constexpr (SOUTER) {            // k-step outer: the first k-step's fragments of both M-tiles first
-#pragma unroll
-    for (int mm = 0; mm < IP_MT; ++mm) a.bias[mm] = load_bias<MODE>(wl, IP_MT * mp + mm), a.sc[mm] = load_scale<MODE>(wl, IP_MT * mp + mm);
-#pragma unroll
-    for (int s = 0; s < Op<MODE>::KSTEPS; ++s)
-#pragma unroll
-      for (int mm = 0; mm < IP_MT; ++mm) a[mm][s] = Op<MODE>::load_a(wl, IP_MT * mp + mm, s, lane);
-    return;
-  }
 #pragma unroll
   for (int mm = 0; mm < IP_MT; ++mm) {
     a.bias[mm] = load_bias<MODE>(wl, IP_MT * mp + mm);
@@ -773,24 +743,9 @@ __device__ __forceinline__ void conv(Tile& tl, int dil, f32x4 (&id)[16 * NBK / 4
   uint32_t sc_l[MT];
 #pragma unroll
   for (int mm = 0; mm < MT; ++mm) bias_l[mm] = a.bias[mm], sc_l[mm] = a.sc[mm];
-  // WalkGeo HALF: the last block holds 64 rows.  RDN_HALF_REMAP = 0: the waves of quarters 2, 3 have no
-  // rows there (wave-uniform) and the others run their two N-tiles; RDN_HALF_REMAP = 1: every wave runs
-  // ONE N-tile of it, rows 16 nq + [0, 16) (its usual B / store addresses moved by -16 nq rows, a multiple
-  // of 16: same swizzle, one address add per access), so the half block costs half a block
-  constexpr bool REMAP = TG::HALF && RDN_HALF_REMAP;
-  static_assert(!REMAP || MODE == MODE_H8, "the half-block remap is written for the f16 + e4m3 write-back");
-  // RDN_TAIL_SWAP: the half block's rows go to the waves of quarters 2-3 (4-7: the younger wave of each
-  // SIMD, which finishes the full blocks last), shifted down by 64 rows, and waves 0-3 idle there instead
-  // -- with RDN_TAIL_EARLY those fetch the next layer's operands in block NB - 2, where they have slack
-  constexpr bool SWAP = TG::HALF && !REMAP && RDN_TAIL_SWAP;
-  const bool half_idle = TG::HALF && !REMAP && ((__builtin_amdgcn_readfirstlane(tid >> 6) >> 1) >= 2) != SWAP;
-  const uint32_t hsw = SWAP && (__builtin_amdgcn_readfirstlane(tid >> 6) >> 1) >= 2 ? 64u * ROWB_F32 : 0u;
-  auto swapped = [&](int j) { return SWAP && j == NB - 1; };
-  const bool stag_late = RDN_TAIL_STAG && __builtin_amdgcn_readfirstlane(tid >> 6) >= 4;
-  constexpr bool SGB = RDN_TAIL_SGB && !RDN_TAIL_STAG && MODE == MODE_H8 && cin && !(EPI & (ADD_ID | SAVE_ID));
-  const uint32_t hoff = REMAP ? (uint32_t)(16 * ROWB_F32) * (uint32_t)__builtin_amdgcn_readfirstlane(nq) : 0u;
-  // the remapped block's rows of this wave start 16 nq, not 32 nq, rows into it
-  auto remapped = [&](int j) { return REMAP && j == NB - 1; };
+  // WalkGeo HALF: the last block holds 64 rows.  The waves of quarters 2, 3 have no rows there
+  // (wave-uniform) and the others run their two N-tiles
+  const bool half_idle = TG::HALF && (__builtin_amdgcn_readfirstlane(tid >> 6) >> 1) >= 2;
   typedef unsigned int u32x4c __attribute__((ext_vector_type(4)));
   u32x4c carry_a = {0u, 0u, 0u, 0u}, carry_b = {0u, 0u, 0u, 0u};
   const bool cwave = WALK && __builtin_amdgcn_readfirstlane(tid >> 6) == THREADS / 64 - 1;
@@ -847,8 +802,6 @@ __device__ __forceinline__ void conv(Tile& tl, int dil, f32x4 (&id)[16 * NBK / 4
   auto read_b = [&](int j, int s, int i) -> typename O::B {
     if (TG::WRAP && j == 0 && s < TS && i == 0) return ldb(bfirst[s], 0);
     if (TG::WRAP && j == NB - 1 && s >= 2 * TS && i == NT - 1) return ldb(blast[s - 2 * TS], 0);
-    if (remapped(j)) return ldb(j >= 2 ? badr2[s] : badr[s], (uint32_t)(BR * (j >= 2 ? j - 2 : j)) * ROWB_F32 - hoff);
-    if (swapped(j)) return ldb(badr2[s], (uint32_t)(BR * (j - 2) + 16 * i) * ROWB_F32 - hsw);
     if (j >= 2) return ldb(badr2[s], (uint32_t)(BR * (j - 2) + 16 * i) * ROWB_F32);
     return ldb(badr[s], (uint32_t)(BR * j + 16 * i) * ROWB_F32);
   };
@@ -897,8 +850,8 @@ __device__ __forceinline__ void conv(Tile& tl, int dil, f32x4 (&id)[16 * NBK / 4
   // stores instead of 6); ReLU folded into the saturating med3
   auto store_pair = [&](int j, int i) {
     if constexpr (MODE == MODE_H8) {                // (instantiated in every mode, called in MODE_H8)
-      const int rb = BR * j + (remapped(j) ? 16 : BR / 4) * nq - (swapped(j) ? 64 : 0);
-      const bool inside = !EDGE || (tl.base + rb >= 0 && tl.base + rb + (remapped(j) ? 16 : BR / 4) <= tl.L);
+      const int rb = BR * j + (BR / 4) * nq;
+      const bool inside = !EDGE || (tl.base + rb >= 0 && tl.base + rb + BR / 4 <= tl.L);
       const bool zero = !inside && !in_range(tl.base + rb + 16 * i + c16, tl.L);
       if (!cout) {                 // plain f16 output (the next layer is uncorrected): no e4m3 planes
         f16x4 hv[MT];
@@ -911,7 +864,7 @@ __device__ __forceinline__ void conv(Tile& tl, int dil, f32x4 (&id)[16 * NBK / 4
           if (EPI & SAVE_ID) id[(j * NT + i) * MT + mm] = v;
           hv[mm] = __builtin_convertvector(v, f16x4);
         }
-        *(f16x8*)(tl.lds + sadr[0][0] + (uint32_t)(BR * j + 16 * i) * ROWB_F32 - (remapped(j) ? hoff : 0u) - (swapped(j) ? hsw : 0u)) =
+        *(f16x8*)(tl.lds + sadr[0][0] + (uint32_t)(BR * j + 16 * i) * ROWB_F32) =
             __builtin_shufflevector(hv[0], hv[1], 0, 1, 2, 3, 4, 5, 6, 7);
         return;
       }
@@ -926,7 +879,7 @@ __device__ __forceinline__ void conv(Tile& tl, int dil, f32x4 (&id)[16 * NBK / 4
         if (EPI & SAVE_ID) id[(j * NT + i) * MT + mm] = v;
         x[mm] = h8_split(v);
       }
-      const uint32_t off = (uint32_t)(BR * j + 16 * i) * ROWB_F32 - (remapped(j) ? hoff : 0u) - (swapped(j) ? hsw : 0u);
+      const uint32_t off = (uint32_t)(BR * j + 16 * i) * ROWB_F32;
       typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
   #if defined(RDN_ABLATE_NOSTORE)
       if (x[0].hi8 == 0x12345678u)
@@ -943,19 +896,11 @@ __device__ __forceinline__ void conv(Tile& tl, int dil, f32x4 (&id)[16 * NBK / 4
   // positions), so the block skips its MFMAs, B reads and write-back (its rows keep older values,
   // which only feed rows beyond L: never stored, never tracked by the range guard)
   auto beyond = [&](int j) { return WALK && EDGE && tl.base + BR * j >= tl.L + 8; };
-  // the block whose k-steps retire this layer's operands, after which the next layer's are fetched: the
-  // last block; RDN_TAIL_EARLY: for the waves that own no rows of a last half block, the block before
-  // (their last use), so half of the CU's operand loads -- bound by the texture path, ~3k cycles per
-  // corrected layer -- leave a block earlier instead of queueing with the others' in the half block
-  auto load_next = [&](int j) {
-    if constexpr (RDN_TAIL_EARLY && TG::HALF && !REMAP) return half_idle ? j == NB - 2 : j == NB - 1;
-    return j == NB - 1;
-  };
   auto store_block = [&](int j) {
     if ((j == NB - 1 && half_idle) || beyond(j)) return;
     if constexpr (MODE == MODE_H8) {
 #pragma unroll
-      for (int i = 0; i < (remapped(j) ? 1 : NT); ++i) store_pair(j, i);
+      for (int i = 0; i < NT; ++i) store_pair(j, i);
     } else {
 #pragma unroll
       for (int i = 0; i < NT; ++i)
@@ -989,7 +934,8 @@ __device__ __forceinline__ void conv(Tile& tl, int dil, f32x4 (&id)[16 * NBK / 4
 #pragma unroll
         for (int mm = 0; mm < MT; ++mm) hi[i][mm] = bias_l[mm];
     }
-    if (has_next && (RDN_TAIL_EARLY >= 2 ? j == NB - 1 : load_next(j))) {   // last use of this layer's bias
+    // the last block's k-steps retire this layer's operands, after which the next layer's are fetched
+    if (has_next && j == NB - 1) {   // last use of this layer's bias
 #pragma unroll
       for (int mm = 0; mm < MT; ++mm) a.bias[mm] = load_bias<MODE>(wnext, MT * mp + mm), a.sc[mm] = load_scale<MODE>(wnext, MT * mp + mm);
     }
@@ -1000,7 +946,7 @@ __device__ __forceinline__ void conv(Tile& tl, int dil, f32x4 (&id)[16 * NBK / 4
     for (int s = 0; s < O::KSTEPS; ++s) {
 #pragma unroll
       for (int i = 0; i < NT; ++i) {
-        if (!skip && !(remapped(j) && i > 0)) {
+        if (!skip) {
 #pragma unroll
         for (int mm = 0; mm < MT; ++mm) {
           if constexpr (MODE == MODE_H8 && !(EPI & (ADD_ID | SAVE_ID))) {
@@ -1025,25 +971,7 @@ __device__ __forceinline__ void conv(Tile& tl, int dil, f32x4 (&id)[16 * NBK / 4
           }
         }
         if (s + 1 < O::KSTEPS) bnext[i] = read_b(j, s + 1, i);
-        else if (j + 1 < NB && !(j + 1 == NB - 1 && half_idle) && !(remapped(j + 1) && i > 0)) bnext[i] = read_b(j + 1, 0, i);
-        }
-        if constexpr (SGB) {
-          if (i == NT - 1 && j >= 2 && s < NT && !beyond(j - 2)) {
-            store_pair(j - 2, s);
-            // MFMA, B read, V VALU (x4), MFMA, V VALU (x2), the three plane stores
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-              __builtin_amdgcn_sched_group_barrier(0x002, RDN_TAIL_SGB, 0);
-            }
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              __builtin_amdgcn_sched_group_barrier(0x002, RDN_TAIL_SGB, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x200, 3, 0);
-          }
+        else if (j + 1 < NB && !(j + 1 == NB - 1 && half_idle)) bnext[i] = read_b(j + 1, 0, i);
         }
         if constexpr (COMP) {
           // fold a finished chunk into the running totals (the rounding error becomes the next
@@ -1065,9 +993,9 @@ __device__ __forceinline__ void conv(Tile& tl, int dil, f32x4 (&id)[16 * NBK / 4
         __builtin_amdgcn_sched_barrier(0);
       }
 #if defined(RDN_ABLATE_NOALOAD_TAIL)       // diagnostic builds only (tools/ablate.py): wrong results
-      if (has_next && load_next(j) && tl.layer < 0) {
+      if (has_next && j == NB - 1 && tl.layer < 0) {
 #else
-      if (has_next && (RDN_TAIL_EARLY == 3 && s > 0 ? j == NB - 1 : load_next(j))) {   // last use of a[.][s]
+      if (has_next && j == NB - 1) {   // last use of a[.][s]
 #endif
 #pragma unroll
         for (int mm = 0; mm < MT; ++mm) {
@@ -1085,16 +1013,8 @@ __device__ __forceinline__ void conv(Tile& tl, int dil, f32x4 (&id)[16 * NBK / 4
       }
       if (j >= 2 && !beyond(j - 2)) {
         constexpr int NP = NT * MT;
-        if constexpr (MODE == MODE_H8 && RDN_TAIL_STAG) {
-          // waves 4-7 (row quarters 2-3) share their SIMDs with waves 0-3: their write-backs run one
-          // k-step later, so the two waves of a SIMD do not issue their e4m3-split VALU together
-          if (!stag_late) {
-            if (s < NT) store_pair(j - 2, s);
-          } else if (s >= 1 && s - 1 < NT) {
-            store_pair(j - 2, s - 1);
-          }
-        } else if constexpr (MODE == MODE_H8) {
-          if (!SGB && s < NT) store_pair(j - 2, s);
+        if constexpr (MODE == MODE_H8) {
+          if (s < NT) store_pair(j - 2, s);
         } else if constexpr (O::KSTEPS >= NP) {
           if (s < NP) store_piece(j - 2, s / MT, s % MT);
         } else {
@@ -1210,25 +1130,19 @@ __device__ __forceinline__ void head_h8_mfma(Tile& tl, const LayerA<MODE_H8>& a,
 // compensates on the plain stacks (1DCNN, RRCDNet, PIDN; measured on the GPU with RDN_F32_CHUNK = 4:
 // trained RRCDNet 1.25e-5 -> 7.4e-6 vs the fp32 reference, 8.1e-6 -> 4.3e-6 vs float64, -8 %
 // throughput).  The residual networks keep one plain chain: DSDN holds 64 VGPRs of identity
-// (compensated it spills 224 B per lane, -11 %), and on the CBAM networks (CbamGeo, RDN_F32_COMP_RES = 1:
-// chunks of RDN_F32_CHUNK_RES k-steps) compensation buys nothing measurable: at inputs x1 - x100 the
-// plain chain is already within 0.65x of the reference fp32's own distance from float64, and at x1000
-// the CBAM gating is chaotic -- the distance is a draw whose size the summation order sets, not its
+// (compensated it spills 224 B per lane, -11 %), and on the CBAM networks (CbamGeo) compensation in
+// chunks of 2 to 6 k-steps was tried and bought nothing measurable: at inputs x1 - x100 the plain
+// chain was already within 0.65x of the reference fp32's own distance from float64, and at x1000
+// the CBAM gating is chaotic -- the distance was a draw whose size the summation order set, not its
 // accuracy (APIDN x1000 vs the reference's distance: plain 5.0x, 6-step chunks 1.6x, 4-step 2.0x,
-// 3-step 6.1x, 2-step 1.4x; against the fp32 noise floor of tests/test_range_gpu.py the plain chain is
+// 3-step 6.1x, 2-step 1.4x; against the fp32 noise floor of tests/test_range_gpu.py the plain chain was
 // the closest of all, 0.95x) -- for -2.3 % (6-step) to -5 % (4-step) of fp32 throughput
 // (profiles/r05/ablate/fp32_rescomp.log).  Split-bf16 / f16f8 error is dominated by the operand split,
 // one chain.
-#ifndef RDN_F32_COMP_RES
-#define RDN_F32_COMP_RES 0
-#endif
-#ifndef RDN_F32_CHUNK_RES
-#define RDN_F32_CHUNK_RES 4
-#endif
 template <int MODE, bool RES> struct Geo { static constexpr int S = 1; };
 template <> struct Geo<MODE_F32, false> { static constexpr int S = RDN_F32_COMP ? 0 : 2; };
 template <int MODE> struct CbamGeo { static constexpr int S = 1; };
-template <> struct CbamGeo<MODE_F32> { static constexpr int S = RDN_F32_COMP && RDN_F32_COMP_RES ? -RDN_F32_CHUNK_RES : 1; };
+template <> struct CbamGeo<MODE_F32> { static constexpr int S = 1; };
 
 // the blob's per-layer correction mask (common.hpp CORR_SLOT), a scalar load
 __device__ __forceinline__ uint64_t corr_mask(const uint8_t* blob) {

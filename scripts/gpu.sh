@@ -3,8 +3,9 @@
 #   STAGES="ab tests" OUT=gpurun_out/r06a bash scripts/gpu.sh
 #
 # Stages (run in the order listed here; the script stops at the first failing stage):
-#   ab          tools/ablate.py A/B of the prebuilt variants in tools/ablate_build (AB_VARIANTS, comma list;
-#               AB_SPECS = arch:dtype pairs; AB_L = spectrum lengths), one process per (spec, L)
+#   ab          tools/ablate.py A/B of the prebuilt variants in tools/ablate_build (AB_VARIANTS, comma list of
+#               tools/ablate.py VARIANTS names, e.g. base,pf2; AB_SPECS = arch:dtype pairs; AB_L = spectrum
+#               lengths), one process per (spec, L)
 #   stamps      phase stamps of the hybrid walk (tools/hyb_stamps.py, a -DRDN_HYB_STAMPS=1 build)
 #   tests       the GPU suite (PYTEST_K: a -k expression)
 #   smoke       __graft_entry__.smoke()

@@ -381,3 +381,27 @@ def test_row_views_and_empty_batches_on_the_host():
         with torch.no_grad():
             y = cls().eval()(x)
         assert tuple(y.shape) == (0, 1, 40), name
+
+
+def test_ablate_variants_name_macros_the_sources_read():
+    """tools/ablate.py VARIANTS: every -DRDN_NAME[=v] a variant passes occurs in a kernel source under
+    csrc/ (a flag nothing reads builds a copy of `base` under another name)."""
+    import glob
+    import importlib.util
+    import re
+    root = os.path.join(os.path.dirname(__file__), "..")
+    spec = importlib.util.spec_from_file_location("ablate", os.path.join(root, "tools", "ablate.py"))
+    ablate = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ablate)
+    text = ""
+    for ext in ("hip", "hpp", "cpp"):
+        for path in glob.glob(os.path.join(ablate.CSRC, "*." + ext)):
+            with open(path) as fh:
+                text += fh.read()
+    assert text
+    words = set(re.findall(r"\bRDN_\w+", text))
+    macros = {(name, m) for name, flags in ablate.VARIANTS.items() for m in re.findall(r"-D(RDN_\w+)", flags)}
+    assert macros
+    assert all(f.startswith("-D") for flags in ablate.VARIANTS.values() for f in flags.split())
+    missing = sorted((name, m) for name, m in macros if m not in words)
+    assert not missing, missing

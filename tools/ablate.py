@@ -1,6 +1,6 @@
 """Diagnostic ablation of the in-place kernels (not part of the product).
 
-Builds libraman_mi355x variants with RDN_ABLATE_* / RDN_IP_NB macros into /tmp and times the RRCDNet
+Builds libraman_mi355x variants with the macros of VARIANTS into tools/ablate_build and times the RRCDNet
 forward of each in ONE process (interleaved rounds), so the deltas say which resource bounds the
 kernel: MFMA issue (NOLDS), LDS traffic (NOMFMA), the write-back (NOSTORE).
 
@@ -15,26 +15,24 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "data-simulation-and-noise-reduction-of-distributed-fiber-raman-intensity_amd", "csrc")
 OUT = os.path.join(ROOT, "tools", "ablate_build")
-VARIANTS = {"base": "", "prev": "", "cur": "", "cur2": "", "nolds": "-DRDN_ABLATE_NOLDS",
-            "nomfma": "-DRDN_ABLATE_NOMFMA", "nostore": "-DRDN_ABLATE_NOSTORE", "noaload": "-DRDN_ABLATE_NOALOAD",
-            "pf3": "-DRDN_H16_PF=3", "ieee": "", "stamps": "-DRDN_TEAM_STAMPS=1", "nobar": "-DRDN_ABLATE_NOBARRIER", "dsdn3": "-DRDN_DSDN_NBK=3", "comp0": "-DRDN_F32_COMP=0",
-            "chunk1": "-DRDN_F32_CHUNK=1", "chunk3": "-DRDN_F32_CHUNK=3", "chunk4": "-DRDN_F32_CHUNK=4",
-            "h16f16": "-DRDN_H16_F16=1", "ld2": "-DRDN_H16_LDSTEP=2", "ld3": "-DRDN_H16_LDSTEP=3", "ld4": "-DRDN_H16_LDSTEP=4", "pf2": "-DRDN_H16_PF=2", "pf4": "-DRDN_H16_PF=4", "alledge": "-DRDN_ABLATE_ALLEDGE -DRDN_TEAM_STAMPS=1",
-            "tail3": "-DRDN_F16MIX_TAIL=3", "tail4": "-DRDN_F16MIX_TAIL=4", "tail5": "-DRDN_F16MIX_TAIL=5", "nowin": "-DRDN_F16MIX_WIN=0", "nostem": "-DRDN_ABLATE_NOSTEM",
-            "tail0": "-DRDN_F16MIX_TAIL=0", "tail2": "-DRDN_F16MIX_TAIL=2", "hybstamps": "-DRDN_HYB_STAMPS=1",
-            "w512": "-DRDN_WALK_ROWS=512", "w448": "-DRDN_WALK_ROWS=448", "mix512": "-DRDN_WALK_ROWS_MIX=512", "mhead": "", "lbar": "", "stg": "", "vote": "", "comb": "", "track": "", "trk2": "", "sdpp": "", "cur": "", "resplain": "", "rescomp0": "-DRDN_F32_COMP_RES=0", "reschunk6": "-DRDN_F32_COMP_RES=1 -DRDN_F32_CHUNK_RES=6", "reschunk3": "-DRDN_F32_COMP_RES=1 -DRDN_F32_CHUNK_RES=3", "reschunk4": "-DRDN_F32_COMP_RES=1 -DRDN_F32_CHUNK_RES=4", "reschunk2": "-DRDN_F32_COMP_RES=1 -DRDN_F32_CHUNK_RES=2", "nozero": "-DRDN_ABLATE_NOZERO", "nozst": "-DRDN_ABLATE_NOZERO -DRDN_TEAM_STAMPS=1", "estag": "-DRDN_H16_ESTAG=1",
-            "prio": "-DRDN_SETPRIO=1", "prio2": "-DRDN_SETPRIO=2", "es3": "-DRDN_H16_ESPLIT=3", "es5": "-DRDN_H16_ESPLIT=5",
-            "sgb2": "-DRDN_H16_SGB=2", "sgb4": "-DRDN_H16_SGB=4", "remap": "-DRDN_HALF_REMAP=1",
-            "prioremap": "-DRDN_SETPRIO=1 -DRDN_HALF_REMAP=1", "tstag": "-DRDN_TAIL_STAG=1",
-            "tsgb1": "-DRDN_TAIL_SGB=1", "tsgb2": "-DRDN_TAIL_SGB=2", "tsgb4": "-DRDN_TAIL_SGB=4", "tsgb8": "-DRDN_TAIL_SGB=8",
-            "stgfirst": "-DRDN_STAGE_FIRST=1",
-            "tearly": "-DRDN_TAIL_EARLY=1", "tearlyhs": "-DRDN_TAIL_EARLY=1 -DRDN_HYB_STAMPS=1",
-            "psw2": "-DRDN_PRIO_SWITCH=2", "psw3": "-DRDN_PRIO_SWITCH=3", "psw4": "-DRDN_PRIO_SWITCH=4",
-            "psw5": "-DRDN_PRIO_SWITCH=5", "psw6": "-DRDN_PRIO_SWITCH=6", "psw4hs": "-DRDN_PRIO_SWITCH=4 -DRDN_HYB_STAMPS=1",
-            "tnoaload": "-DRDN_ABLATE_NOALOAD_TAIL", "tnoaloadhs": "-DRDN_ABLATE_NOALOAD_TAIL -DRDN_HYB_STAMPS=1",
-            "tswap": "-DRDN_TAIL_SWAP=1", "tswapearly": "-DRDN_TAIL_SWAP=1 -DRDN_TAIL_EARLY=1",
-            "tswapearlyhs": "-DRDN_TAIL_SWAP=1 -DRDN_TAIL_EARLY=1 -DRDN_HYB_STAMPS=1",
-            "tswape2": "-DRDN_TAIL_SWAP=1 -DRDN_TAIL_EARLY=2", "tswape3": "-DRDN_TAIL_SWAP=1 -DRDN_TAIL_EARLY=3"}
+VARIANTS = {
+    # no flags: "base" (run's reference output), "prev" and "ieee" (other sources / other flags, see build)
+    "base": "", "prev": "", "ieee": "",
+    # diagnostic builds (wrong results by design) and instruments (tools/team_stamps.py, tools/hyb_stamps.py)
+    "nolds": "-DRDN_ABLATE_NOLDS", "nomfma": "-DRDN_ABLATE_NOMFMA", "nostore": "-DRDN_ABLATE_NOSTORE",
+    "noaload": "-DRDN_ABLATE_NOALOAD", "nobar": "-DRDN_ABLATE_NOBARRIER", "nozero": "-DRDN_ABLATE_NOZERO",
+    "nostem": "-DRDN_ABLATE_NOSTEM", "tnoaload": "-DRDN_ABLATE_NOALOAD_TAIL",
+    "tnoaloadhs": "-DRDN_ABLATE_NOALOAD_TAIL -DRDN_HYB_STAMPS=1", "hybstamps": "-DRDN_HYB_STAMPS=1",
+    "stamps": "-DRDN_TEAM_STAMPS=1", "alledge": "-DRDN_ABLATE_ALLEDGE -DRDN_TEAM_STAMPS=1",
+    "nozst": "-DRDN_ABLATE_NOZERO -DRDN_TEAM_STAMPS=1",
+    # geometry and numerics parameters
+    "h16f16": "-DRDN_H16_F16=1", "pf2": "-DRDN_H16_PF=2", "pf3": "-DRDN_H16_PF=3", "pf4": "-DRDN_H16_PF=4",
+    "ld2": "-DRDN_H16_LDSTEP=2", "ld3": "-DRDN_H16_LDSTEP=3", "ld4": "-DRDN_H16_LDSTEP=4", "dsdn3": "-DRDN_DSDN_NBK=3",
+    "comp0": "-DRDN_F32_COMP=0", "chunk1": "-DRDN_F32_CHUNK=1", "chunk3": "-DRDN_F32_CHUNK=3", "chunk4": "-DRDN_F32_CHUNK=4",
+    "tail0": "-DRDN_F16MIX_TAIL=0", "tail2": "-DRDN_F16MIX_TAIL=2", "tail3": "-DRDN_F16MIX_TAIL=3",
+    "tail4": "-DRDN_F16MIX_TAIL=4", "tail5": "-DRDN_F16MIX_TAIL=5", "nowin": "-DRDN_F16MIX_WIN=0",
+    "w512": "-DRDN_WALK_ROWS=512", "w448": "-DRDN_WALK_ROWS=448", "mix512": "-DRDN_WALK_ROWS_MIX=512",
+}
 
 
 def build():

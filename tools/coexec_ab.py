@@ -5,7 +5,10 @@ launches of the same kernel, in ABLATE_ONLY order.  This script assigns the kern
 variants by that order and reports, per variant, the mean of every counter and the ratios DESIGN cites
 (MFMA busy of SIMD cycles, VALU-MFMA co-execution share of the MFMA-busy cycles).
 
-    python tools/coexec_ab.py gpurun_out/final6 rdn::h16fw::rrcdnet_walk base,prio > profiles/r06/rocprof/coexec_ab.json
+    python tools/coexec_ab.py <dir holding the coexec_* profiler outputs> rdn::h16fw::rrcdnet_walk base,pf2 > coexec_ab.json
+
+profiles/r06/rocprof/coexec_ab.json is this script's output for base,prio; the `prio` variant (static
+wave priority) was last buildable at 3a33a0e.
 """
 import csv
 import glob
