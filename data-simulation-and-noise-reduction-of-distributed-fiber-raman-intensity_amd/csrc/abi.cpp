@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include "netspec.hpp"
 #include "host_util.hpp"
+#include "snr.hpp"
 
 namespace rdn {
 std::string pack(int arch, int dtype, const float* const* tensors, const int64_t* numels, int n, void* dst, size_t cap);
@@ -44,6 +45,8 @@ hipError_t launch_generate(uint64_t seed, uint64_t first, int64_t n, int L, floa
                            int max_repeat, float* clean, float* noisy, float* snr, float* nstd, hipStream_t s);
 hipError_t launch_metrics(const float* y, const void* clean, bool clean_f64, int64_t n, int L, double* per, double* sums,
                           long long* acc, hipStream_t s);
+hipError_t launch_snr(const float* x, const float* y, const void* clean, bool clean_f64, int64_t n, int L,
+                      const snr::SnrOut& so, hipStream_t s);
 }  // namespace rdn
 
 namespace {
@@ -456,6 +459,64 @@ int rdn_acc_value(const int64_t* acc, double* sums) {
     sums[k] = a[RDN_ACC_LIMBS] ? std::nan("") : acc_to_double(a);
   }
   sums[4] = (double)acc[RDN_ACC_COUNT];
+  return RDN_OK;
+  RDN_GUARD_END
+}
+
+static bool valid_bins(float lo, float hi, int nbins) {
+  return nbins >= 1 && nbins <= RDN_REPORT_MAX_BINS && std::isfinite(lo) && std::isfinite(hi) && lo < hi &&
+         std::isfinite(hi - lo);
+}
+static const char* bins_msg() { return "need 1 <= nbins <= 64 and finite lo < hi"; }
+
+int rdn_snr(const float* x, const float* y, const void* clean, int clean_is_f64, int64_t n, int64_t L,
+            double* per_spectrum3, const float* key, float lo, float hi, int nbins, const double* per4,
+            int64_t* report, void* stream) {
+  RDN_GUARD_BEGIN
+  if (n > 0 && (!x || !y || !clean)) return fail(RDN_EINVAL, "rdn_snr: null pointer");
+  if (clean_is_f64 != 0 && clean_is_f64 != 1) return fail(RDN_EINVAL, "rdn_snr: clean_is_f64 must be 0 or 1");
+  if (n < 0 || L < 1 || L > 0x7fffffff) return fail(RDN_EINVAL, "rdn_snr: need n >= 0 and 1 <= L < 2^31");
+  if (report && !valid_bins(lo, hi, nbins)) return fail(RDN_EINVAL, std::string("rdn_snr: ") + bins_msg());
+  if (!report && (key || per4)) return fail(RDN_EINVAL, "rdn_snr: key / per4 feed the report, which is NULL");
+  if (!report && !per_spectrum3) return fail(RDN_EINVAL, "rdn_snr: neither per_spectrum3 nor report to write");
+  if (n == 0) return RDN_OK;
+  const rdn::snr::SnrOut so{per_spectrum3, key, per4, (long long*)report,
+                            report ? rdn::snr::make_bins(lo, hi, nbins) : rdn::snr::Bins{0.f, 0.f, 0.f, 0}};
+  return hip_check(rdn::launch_snr(x, y, clean, clean_is_f64 == 1, n, (int)L, so, (hipStream_t)stream), "snr");
+  RDN_GUARD_END
+}
+
+int rdn_report_bin(float key, float lo, float hi, int nbins, int* row) {
+  RDN_GUARD_BEGIN
+  if (!row) return fail(RDN_EINVAL, "rdn_report_bin: null pointer");
+  if (!valid_bins(lo, hi, nbins)) return fail(RDN_EINVAL, std::string("rdn_report_bin: ") + bins_msg());
+  *row = rdn::snr::bin_row(key, rdn::snr::make_bins(lo, hi, nbins));
+  return RDN_OK;
+  RDN_GUARD_END
+}
+
+int rdn_report_value(const int64_t* report, int nbins, double* out) {
+  RDN_GUARD_BEGIN
+  if (!report || !out) return fail(RDN_EINVAL, "rdn_report_value: null pointer");
+  if (nbins < 1 || nbins > RDN_REPORT_MAX_BINS) return fail(RDN_EINVAL, "rdn_report_value: need 1 <= nbins <= 64");
+  const int rows = RDN_REPORT_ROWS(nbins);
+  // the totals row: integer sums of the rows' words (at most 66 rows of |limb| < 2^63 / 66: a report
+  // holds up to 2^31 spectra of 32-bit chunks), added without sign overflow in unsigned arithmetic
+  int64_t total[RDN_REPORT_ROW_WORDS] = {};
+  auto values = [](const int64_t* r, double* o) {
+    o[0] = (double)r[RDN_REPORT_COUNT];
+    for (int k = 0; k < RDN_REPORT_QUANTITIES; ++k) {
+      const int64_t* a = r + k * RDN_ACC_STRIDE;
+      o[1 + k] = a[RDN_ACC_LIMBS] ? std::nan("") : acc_to_double(a);
+    }
+    o[1 + RDN_REPORT_QUANTITIES] = (double)r[RDN_REPORT_COUNT4];
+  };
+  for (int b = 0; b < rows; ++b) {
+    const int64_t* r = report + (size_t)b * RDN_REPORT_ROW_WORDS;
+    values(r, out + (size_t)b * RDN_REPORT_VALUES);
+    for (int w = 0; w < RDN_REPORT_ROW_WORDS; ++w) total[w] = (int64_t)((uint64_t)total[w] + (uint64_t)r[w]);
+  }
+  values(total, out + (size_t)rows * RDN_REPORT_VALUES);
   return RDN_OK;
   RDN_GUARD_END
 }

@@ -7,7 +7,9 @@
 // tensors.bin: for each name of rdn_param_names(arch), in order: int64 numel, then numel float32
 // (written by tests/test_abi.py::test_host_sanitizer_pack).  The packed blob is written to
 // blob_out.bin so that the test can compare it byte for byte with the library's own rdn_pack.
-// Then the error paths: wrong numel, too-small destination, null pointers, bad arch/dtype.
+// Then the error paths: wrong numel, too-small destination, null pointers, bad arch/dtype; and the
+// host side of the SNR report (rdn_snr's argument checks, rdn_report_bin, rdn_report_value on an
+// exactly-sized report).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -93,6 +95,35 @@ int main(int argc, char** argv) {
                      nullptr) == RDN_EINVAL);
   EXPECT(rdn_metrics(nullptr, nullptr, 1, 100, nullptr, nullptr, nullptr) == RDN_EINVAL);
   EXPECT(rdn_generate(0, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == RDN_EINVAL);
+  // SNR report: argument checks, the bin formula and the host conversion of an exactly-sized report
+  {
+    const int nb = 3;
+    std::vector<int64_t> rep(RDN_REPORT_WORDS(nb), 0);
+    std::vector<double> val((RDN_REPORT_ROWS(nb) + 1) * RDN_REPORT_VALUES, -1.0);
+    EXPECT(rdn_snr(nullptr, nullptr, nullptr, 0, 1, 100, nullptr, nullptr, 20.f, 37.f, nb, nullptr, rep.data(), nullptr) ==
+           RDN_EINVAL);
+    EXPECT(rdn_snr(nullptr, nullptr, nullptr, 0, 0, 100, nullptr, nullptr, 20.f, 37.f, 65, nullptr, rep.data(), nullptr) ==
+           RDN_EINVAL);
+    EXPECT(rdn_snr(nullptr, nullptr, nullptr, 0, 0, 100, nullptr, nullptr, 20.f, 37.f, nb, nullptr, rep.data(), nullptr) ==
+           RDN_OK);
+    int row = -1;
+    EXPECT(rdn_report_bin(20.f, 20.f, 37.f, nb, &row) == RDN_OK && row == 1);
+    EXPECT(rdn_report_bin(37.f, 20.f, 37.f, nb, &row) == RDN_OK && row == nb + 1);
+    EXPECT(rdn_report_bin(19.f, 20.f, 37.f, nb, &row) == RDN_OK && row == 0);
+    EXPECT(rdn_report_bin(1.f, 2.f, 2.f, nb, &row) == RDN_EINVAL);
+    // 1.5 in row 2's SNR_in (limb 4 holds the units: weight 2^(32 * 4 - 128)), -0.5 in the overflow row's
+    int64_t* r2 = rep.data() + 2 * RDN_REPORT_ROW_WORDS + 4 * RDN_ACC_STRIDE;
+    r2[4] = 1, r2[3] = (int64_t)1 << 31;
+    rep[2 * RDN_REPORT_ROW_WORDS + RDN_REPORT_COUNT] = 1;
+    int64_t* r4 = rep.data() + (nb + 1) * RDN_REPORT_ROW_WORDS + 4 * RDN_ACC_STRIDE;
+    r4[3] = -((int64_t)1 << 31);
+    rep[(nb + 1) * RDN_REPORT_ROW_WORDS + RDN_REPORT_COUNT] = 1;
+    EXPECT(rdn_report_value(rep.data(), nb, val.data()) == RDN_OK);
+    EXPECT(val[2 * RDN_REPORT_VALUES + 5] == 1.5 && val[(nb + 1) * RDN_REPORT_VALUES + 5] == -0.5);
+    EXPECT(val[(nb + 2) * RDN_REPORT_VALUES] == 2.0 && val[(nb + 2) * RDN_REPORT_VALUES + 5] == 1.0);
+    EXPECT(rdn_report_value(rep.data(), 0, val.data()) == RDN_EINVAL);
+    EXPECT(rdn_report_value(nullptr, nb, val.data()) == RDN_EINVAL);
+  }
 
   if (fails) return 1;
   std::printf("host_check: arch %d dtype %d: %zu tensors, %zu bytes packed, all checks passed\n", arch, dtype,

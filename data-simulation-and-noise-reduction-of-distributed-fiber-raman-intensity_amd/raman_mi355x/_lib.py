@@ -25,6 +25,21 @@ ACC_STRIDE = ACC_LIMBS + 1
 ACC_COUNT = 4 * ACC_STRIDE
 ACC_WORDS = ACC_COUNT + 1
 ACC_FRAC_BITS = 128
+# SNR report words (include/raman_mi355x.h RDN_REPORT_*)
+REPORT_QUANTITIES = 7
+REPORT_MAX_BINS = 64
+REPORT_COUNT = REPORT_QUANTITIES * ACC_STRIDE
+REPORT_COUNT4 = REPORT_COUNT + 1
+REPORT_ROW_WORDS = REPORT_COUNT4 + 1
+REPORT_VALUES = REPORT_QUANTITIES + 2
+
+
+def report_rows(nbins):
+    return nbins + 2
+
+
+def report_words(nbins):
+    return report_rows(nbins) * REPORT_ROW_WORDS
 
 
 def source_hash():
@@ -83,6 +98,13 @@ _SIGNATURES = {
     "rdn_metrics_ex": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rdn_acc_value": ([ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+    # the SNR report: added to ABI v6 without a version bump, detected by symbol (lib())
+    "rdn_snr": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_void_p,
+                 ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rdn_report_bin": ([ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
+                       ctypes.c_int),
+    "rdn_report_value": ([ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGNATURES)
@@ -98,6 +120,10 @@ def lib():
             raise ImportError(f"raman_mi355x native library not built: {LIB_PATH} is missing "
                               "(run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C csrc`)")
         handle = ctypes.CDLL(LIB_PATH)
+        missing = [name for name in _SIGNATURES if not hasattr(handle, name)]
+        if missing:
+            raise ImportError(f"libraman_mi355x.so lacks {', '.join(missing)}: it was built from older sources; "
+                              "rebuild it (make -C csrc, or __graft_entry__.build())")
         for name, (args, res) in _SIGNATURES.items():
             fn = getattr(handle, name)
             fn.argtypes = args

@@ -442,3 +442,104 @@ def acc_value(acc):
     _lib.check(_lib.lib().rdn_acc_value(ctypes.cast(h.data_ptr(), ctypes.POINTER(ctypes.c_int64)),
                                         ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_double))), "rdn_acc_value")
     return out
+
+
+# ---- SNR report (rdn_snr; definitions, bin formula and report layout: include/raman_mi355x.h) ----
+REPORT_QUANTITIES = ("MSE", "SSIM", "Smoothness", "Peak2Peak", "SNR_in", "SNR_out", "SNR_gain")
+
+
+def _bins(bins):
+    """(lo, hi, nbins) as rdn_snr takes them: finite fp32 lo < hi, 1 <= nbins <= 64."""
+    try:
+        lo, hi, nbins = bins
+    except (TypeError, ValueError):
+        raise ValueError(f"bins must be (lo, hi, nbins), got {bins!r}") from None
+    if isinstance(nbins, bool) or int(nbins) != nbins or not 1 <= int(nbins) <= _lib.REPORT_MAX_BINS:
+        raise ValueError(f"nbins must be an integer in [1, {_lib.REPORT_MAX_BINS}], got {nbins!r}")
+    lo, hi = ctypes.c_float(lo).value, ctypes.c_float(hi).value      # the fp32 edges the kernel bins by
+    if not (lo < hi and abs(lo) != float("inf") and abs(hi) != float("inf")):
+        raise ValueError(f"bins need finite lo < hi, got ({lo}, {hi})")
+    return lo, hi, int(nbins)
+
+
+def new_report(nbins, device):
+    """A zeroed SNR report (RDN_REPORT_WORDS(nbins) int64: nbins + 2 rows) on ``device``."""
+    if isinstance(nbins, bool) or int(nbins) != nbins or not 1 <= int(nbins) <= _lib.REPORT_MAX_BINS:
+        raise ValueError(f"nbins must be an integer in [1, {_lib.REPORT_MAX_BINS}], got {nbins!r}")
+    return torch.zeros(_lib.report_words(int(nbins)), dtype=torch.int64, device=device)
+
+
+def report_bin(key, bins):
+    """Report row (0 underflow, 1 .. nbins, nbins + 1 overflow / NaN) of a key: rdn_report_bin, the
+    kernel's own fp32 formula evaluated on the host."""
+    lo, hi, nbins = _bins(bins)
+    row = ctypes.c_int(-1)
+    _lib.check(_lib.lib().rdn_report_bin(float(key), lo, hi, nbins, ctypes.byref(row)), "rdn_report_bin")
+    return row.value
+
+
+def report_value(report, nbins):
+    """Doubles of a report (float64 (nbins + 3, 9), CPU): one row per report row -- underflow, the bins,
+    overflow -- then the totals over all of them; columns {count, ΣMSE, ΣSSIM, ΣSmoothness, ΣPeak2Peak,
+    ΣSNR_in, ΣSNR_out, ΣSNR_gain, count of spectra whose four metrics were supplied}.  Each sum is the
+    exact total rounded once, NaN where a value was out of range (rdn_report_value)."""
+    nbins = int(nbins)
+    if not 1 <= nbins <= _lib.REPORT_MAX_BINS:
+        raise ValueError(f"nbins must be in [1, {_lib.REPORT_MAX_BINS}], got {nbins}")
+    h = report.detach().to("cpu", torch.int64).contiguous()
+    if h.numel() != _lib.report_words(nbins):
+        raise ValueError(f"a report of {nbins} bins has {_lib.report_words(nbins)} words, got {h.numel()}")
+    out = torch.empty((_lib.report_rows(nbins) + 1, _lib.REPORT_VALUES), dtype=torch.float64)
+    _lib.check(_lib.lib().rdn_report_value(ctypes.cast(h.data_ptr(), ctypes.POINTER(ctypes.c_int64)), nbins,
+                                           ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_double))),
+               "rdn_report_value")
+    return out
+
+
+def snr(x, y, clean, key=None, bins=None, per4=None, report=None, per_spectrum=True):
+    """Per-spectrum [SNR_in, SNR_out, SNR_gain] in dB (fp64, (n, 3)) of the noisy input ``x`` and the
+    denoised ``y`` (float32) against ``clean`` (float32 or float64), with P = mean(clean²), and -- with
+    ``bins`` = (lo, hi, nbins) -- the stratified report this batch is added to (rdn_snr).
+
+    ``key``: float32 (n,), the value each spectrum is binned by (the nominal SNR of generate() or of a
+    dataset's ``snrs``); None bins by the measured SNR_in.  ``per4``: the float64 (n, 4) per-spectrum
+    output of metrics() / forward_metrics() for the same spectra, added to the bins' first four
+    accumulators.  ``report``: a report of new_report(nbins) to accumulate into (made when None).
+    Returns (per (n, 3) or None, report or None)."""
+    _check_cuda_f32(x, "input")
+    _check_cuda_f32(y, "denoised")
+    if not (torch.is_tensor(clean) and clean.is_cuda):
+        raise RuntimeError("raman_mi355x runs on the GPU only: clean must be a CUDA (HIP) tensor")
+    if clean.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"clean must be float32 or float64, got {clean.dtype}")
+    x, y, clean = _rows(x), _rows(y), _rows(clean)
+    if x.shape != y.shape or y.shape != clean.shape:
+        raise ValueError(f"shape mismatch {tuple(x.shape)} vs {tuple(y.shape)} vs {tuple(clean.shape)}")
+    n, L = y.shape
+    if L < 1:
+        raise ValueError("spectra must have at least one sample")
+    dev = y.device
+    if x.device != dev or clean.device != dev:
+        raise ValueError(f"denoised on {dev} but input on {x.device} and clean on {clean.device}")
+    if bins is None:
+        if key is not None or per4 is not None or report is not None:
+            raise ValueError("key, per4 and report feed the binned report: pass bins=(lo, hi, nbins)")
+        if not per_spectrum:
+            raise ValueError("nothing to compute: per_spectrum=False and no bins")
+        lo = hi = 0.0
+        nbins = 0
+    else:
+        lo, hi, nbins = _bins(bins)
+        if report is None:
+            report = new_report(nbins, dev)
+        else:
+            _check_out(report, "report", (_lib.report_words(nbins),), dev, torch.int64)
+        if key is not None:
+            _check_out(key, "key", (n,), dev, torch.float32)
+        if per4 is not None:
+            _check_out(per4, "per4", (n, 4), dev, torch.float64)
+    per = torch.empty((n, 3), dtype=torch.float64, device=dev) if per_spectrum else None
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+    _lib.check(_lib.lib().rdn_snr(ptr(x), ptr(y), ptr(clean), int(clean.dtype == torch.float64), n, L, ptr(per),
+                                  ptr(key), lo, hi, nbins, ptr(per4), ptr(report), _stream(dev)), "rdn_snr")
+    return per, report

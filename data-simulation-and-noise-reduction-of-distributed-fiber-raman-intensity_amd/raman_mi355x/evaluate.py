@@ -58,6 +58,40 @@ def means_from_acc(acc):
     return {k: s[i] / s[4] for i, k in enumerate(KEYS)}
 
 
+SNR_KEYS = ("SNR_in", "SNR_out", "SNR_gain")
+# what snr_bins adds to a result (write_metrics leaves them to write_snr_report)
+_SNR_RESULT_KEYS = SNR_KEYS + ("by_snr", "snr_under", "snr_over")
+
+
+def snr_summary(report, bins):
+    """What ``snr_bins`` adds to a result, from an (all-reduced) report: the means of SNR_in, SNR_out and
+    SNR_gain over all spectra (dB), and ``by_snr``: one entry per bin with its edges ``lo`` / ``hi``, its
+    ``count`` and -- unless the bin is empty -- the seven means (the four metrics only where per-spectrum
+    metrics were supplied).  ``snr_under`` / ``snr_over`` are the same entries for keys below ``lo`` and
+    at or above ``hi`` (or NaN).  A mean over values that include a non-finite one is NaN."""
+    lo, hi, nbins = engine._bins(bins)
+    v = engine.report_value(report, nbins).tolist()
+
+    def entry(row, e_lo, e_hi):
+        count, count4 = int(row[0]), int(row[_lib.REPORT_VALUES - 1])
+        e = {"lo": e_lo, "hi": e_hi, "count": count}
+        for i, k in enumerate(engine.REPORT_QUANTITIES):
+            c = count4 if i < 4 else count
+            if c > 0:
+                e[k] = row[1 + i] / c
+        return e
+
+    edges = np.linspace(np.float64(lo), np.float64(hi), nbins + 1).tolist()
+    total = entry(v[nbins + 2], float("-inf"), float("inf"))
+    if total["count"] <= 0:
+        raise ValueError("no spectra were evaluated")
+    out = {k: total[k] for k in SNR_KEYS}
+    out["by_snr"] = [entry(v[1 + b], edges[b], edges[b + 1]) for b in range(nbins)]
+    out["snr_under"] = entry(v[0], float("-inf"), lo)
+    out["snr_over"] = entry(v[nbins + 1], hi, float("inf"))
+    return out
+
+
 def _engine_module(model):
     """A raman_mi355x network whose own forward is the engine (not a subclass overriding forward)."""
     from .models import _EngineNet
@@ -82,11 +116,16 @@ def _workspace(model, n, L, device):
     return engine.Workspace(model.ARCH, model.engine_code, n, L, device)
 
 
-def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None):
+def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bins=None, snrs=None):
     """evaulate.py:25-39 batched on the device.  Inputs beyond the 16-bit modes' domain (|x| > 4) or
     activations beyond the e4m3 planes' range raise RangeError after the run (one check at the end,
     no per-batch wait) -- unlike the module's own forward, which re-runs such a batch in fp32: evaluate
-    such data with the module in 'fp32'."""
+    such data with the module in 'fp32'.
+
+    ``snr_bins`` = (lo, hi, nbins) additionally runs the SNR pass on every batch (engine.snr) and adds
+    snr_summary's keys to the result: the mean SNR_in, SNR_out and SNR_gain in dB and ``by_snr``, the
+    seven means per bin of ``snrs`` -- the dataset's nominal SNR per spectrum (the ``snrs`` array of a
+    test.npz), or, when None, the measured SNR_in.  The report is all-reduced like the accumulator."""
     model.eval()
     if device is None:
         device = next(model.parameters()).device
@@ -101,6 +140,15 @@ def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None):
         raise RuntimeError("raman_mi355x.evaluate runs its metrics on the GPU; on a CPU device use the module "
                            "itself in the reference's evaulate.py loop (its forward falls back to eager PyTorch)")
     acc = engine.new_acc(device)
+    report = None
+    if snr_bins is not None:
+        report = engine.new_report(engine._bins(snr_bins)[2], device)
+        if snrs is not None:
+            snrs = torch.as_tensor(np.asarray(snrs.cpu() if torch.is_tensor(snrs) else snrs), dtype=torch.float32).reshape(-1)
+            if snrs.numel() != noisy.shape[0]:
+                raise ValueError(f"snrs has {snrs.numel()} values for {noisy.shape[0]} spectra")
+    elif snrs is not None:
+        raise ValueError("snrs is the binning key of the SNR report: pass snr_bins=(lo, hi, nbins)")
     ws = _workspace(model, min(batch_size, max(hi - lo, 1)), L, device)
     # fp64 clean stays fp64 (the metrics compare against the same float64 values as evaulate.py)
     cdt = torch.float64 if (clean.dtype == torch.float64 if torch.is_tensor(clean) else clean.dtype == np.float64) \
@@ -112,18 +160,24 @@ def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None):
             c = torch.as_tensor(clean[b0:b1], dtype=cdt).to(device)
             if _engine_module(model) and model.uses_engine(x):
                 # the engine's forward + metric sums (fused into the forward kernel on the walk geometry)
-                engine.forward_metrics(model.ARCH, model.engine_code, model.packed_weights(x.device), x, c, acc=acc,
-                                       check=False, workspace=ws)
+                y, per, _, _ = engine.forward_metrics(model.ARCH, model.engine_code, model.packed_weights(x.device), x, c,
+                                                      acc=acc, per_spectrum=report is not None, check=False, workspace=ws)
             else:
                 y = model(x)
-                engine.metrics(y.squeeze(1), c, per_spectrum=False, acc=acc)
+                per, _ = engine.metrics(y.squeeze(1), c, per_spectrum=report is not None, acc=acc)
+            if report is not None:
+                key = snrs[b0:b1].to(device) if snrs is not None else None
+                engine.snr(x, y, c, key=key, bins=snr_bins, per4=per, report=report, per_spectrum=False)
     _finish(model, ws)
     _all_reduce_acc(acc)
-    return means_from_acc(acc)
+    means = means_from_acc(acc)
+    if report is not None:
+        means.update(snr_summary(_all_reduce_acc(report), snr_bins))
+    return means
 
 
 def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_size=8192, device=None,
-                       first_index=0, gen_kwargs=None, log_every_s=0.0, fused_metrics=True):
+                       first_index=0, gen_kwargs=None, log_every_s=0.0, fused_metrics=True, snr_bins=None):
     """Config 4: ``total`` simulator spectra [first_index, first_index + total),
     sharded over the ranks as [r·N/W, (r+1)·N/W), each chunk generated on the device, denoised by
     every model in ``models`` (name -> module) and metered into that model's exact accumulator.
@@ -131,7 +185,11 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
     (identical for any world size) and the max-over-ranks wall time of the loop.  ``log_every_s`` > 0
     prints progress to stderr about that often (the loop then waits for the device every 64 chunks,
     so the printed count is what the GPU has finished).  ``fused_metrics=False`` meters with the separate
-    metrics kernel after each forward (the A/B of the metric epilogue; the same bits)."""
+    metrics kernel after each forward (the A/B of the metric epilogue; the same bits).
+    ``snr_bins`` = (lo, hi, nbins) additionally runs the SNR pass on every chunk, binned by the
+    generator's nominal SNR (its ``snr_db``), and adds snr_summary's keys (SNR_in, SNR_out, SNR_gain,
+    by_snr, ...) and the all-reduced ``report`` words to each model's entry -- the same bits for any world
+    size or batch size, like the means."""
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
@@ -148,6 +206,7 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
         for name, model in models.items():
             model.eval()
             acc = engine.new_acc(device)
+            report = engine.new_report(engine._bins(snr_bins)[2], device) if snr_bins is not None else None
             ws = _workspace(model, B, L, device)
             packed = model.packed_weights(device)
             if dist.is_available() and dist.is_initialized():
@@ -163,17 +222,21 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
                         print(f"[evaluate_synthetic rank {rank}] {name}: {b0 - lo} / {hi - lo} spectra, "
                               f"{t_log - t0:.1f} s", file=sys.stderr, flush=True)
                 nb = min(B, hi - b0)
-                engine.generate(nb, seed, first_index=first_index + b0, signal_length=L, device=device,
-                                out=(clean[:nb], noisy[:nb]), **gen_kwargs)
+                _, _, snr_db, _ = engine.generate(nb, seed, first_index=first_index + b0, signal_length=L, device=device,
+                                                  out=(clean[:nb], noisy[:nb]), **gen_kwargs)
                 # forward + metric sums in one call: on the walk geometry the forward kernel meters each
                 # spectrum itself (no second pass over y); otherwise the metrics kernel follows it
                 if fused_metrics:
-                    engine.forward_metrics(model.ARCH, model.engine_code, packed, noisy[:nb].view(nb, 1, L),
-                                           clean[:nb], out=y[:nb], acc=acc, check=False, workspace=ws)
+                    _, per, _, _ = engine.forward_metrics(model.ARCH, model.engine_code, packed, noisy[:nb].view(nb, 1, L),
+                                                          clean[:nb], out=y[:nb], acc=acc, per_spectrum=report is not None,
+                                                          check=False, workspace=ws)
                 else:
                     engine.forward(model.ARCH, model.engine_code, packed, noisy[:nb].view(nb, 1, L), out=y[:nb],
                                    check=False, workspace=ws)
-                    engine.metrics(y[:nb].view(nb, L), clean[:nb], per_spectrum=False, acc=acc)
+                    per, _ = engine.metrics(y[:nb].view(nb, L), clean[:nb], per_spectrum=report is not None, acc=acc)
+                if report is not None:
+                    engine.snr(noisy[:nb], y[:nb], clean[:nb], key=snr_db, bins=snr_bins, per4=per, report=report,
+                               per_spectrum=False)
             _finish(model, ws)              # waits for the stream; raises on a timed-out hand-off / range / gate
             torch.cuda.synchronize(device)
             el = time.perf_counter() - t0
@@ -186,13 +249,41 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
             el = float(t.item())
             out[name] = {"means": means_from_acc(acc), "acc": acc.cpu().tolist(), "spectra": int(total),
                          "seconds": el, "spectra_per_s": total / el if el > 0 else None}
+            if report is not None:
+                _all_reduce_acc(report)
+                out[name].update(snr_summary(report, snr_bins))
+                out[name]["report"] = report.cpu().tolist()
     return out
 
 
 def write_metrics(metrics, root="eval_results"):
+    """evaulate.py:78-80's metrics.txt; what ``snr_bins`` added to a result goes to write_snr_report."""
     save_dir = os.path.join(root, datetime.now().strftime("%Y%m%d_%H%M%S"))
     os.makedirs(save_dir, exist_ok=True)
     with open(os.path.join(save_dir, "metrics.txt"), "w") as f:
         for k, v in metrics.items():
-            f.write(f"{k}: {v:.6f}\n")
+            if k not in _SNR_RESULT_KEYS:
+                f.write(f"{k}: {v:.6f}\n")
     return save_dir
+
+
+def write_snr_report(result, root):
+    """Write the SNR part of an ``evaluate(..., snr_bins=...)`` result into the directory ``root`` (e.g.
+    the one write_metrics returned, beside its metrics.txt): ``snr_report.json`` (the SNR keys as they
+    are) and ``snr_report.txt``, a table with one line per bin."""
+    import json
+    if "by_snr" not in result:
+        raise ValueError("the result has no SNR report: evaluate with snr_bins=(lo, hi, nbins)")
+    os.makedirs(root, exist_ok=True)
+    part = {k: result[k] for k in _SNR_RESULT_KEYS}
+    with open(os.path.join(root, "snr_report.json"), "w") as f:
+        json.dump(part, f, indent=1)
+    cols = engine.REPORT_QUANTITIES
+    with open(os.path.join(root, "snr_report.txt"), "w") as f:
+        for k in SNR_KEYS:
+            f.write(f"{k}: {result[k]:.6f}\n")
+        f.write("lo hi count " + " ".join(cols) + "\n")
+        for e in [result["snr_under"]] + list(result["by_snr"]) + [result["snr_over"]]:
+            f.write(f"{e['lo']:.4f} {e['hi']:.4f} {e['count']} "
+                    + " ".join(f"{e[k]:.6f}" if k in e else "-" for k in cols) + "\n")
+    return root

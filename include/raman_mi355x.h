@@ -248,6 +248,66 @@ int rdn_metrics_ex(const float* y, const void* clean, int clean_is_f64, int64_t 
  * out-of-range value). */
 int rdn_acc_value(const int64_t* acc, double* sums);
 
+/* ---- SNR report (entry points added to ABI v6 without a version bump: detect them by symbol) -------
+ *
+ * Per spectrum, in fp64, from the noisy input x (fp32), the denoised y (fp32) and clean (fp32 / fp64):
+ *   P  = mean(clean^2)              the simulator's own signal power, 数据集产生.py:43
+ *   Ni = mean((x - clean)^2)        No = mean((y - clean)^2)
+ *   SNR_in = 10 log10(P / Ni)       SNR_out = 10 log10(P / No)       SNR_gain = SNR_out - SNR_in   [dB]
+ * A zero denominator or a zero P gives the IEEE result (+-inf or NaN), written as it is to the
+ * per-spectrum output and counted in the out-of-range word of that quantity in a report: never clamped.
+ *
+ * Report: RDN_REPORT_WORDS(nbins) int64 on the device, RDN_REPORT_ROWS(nbins) = nbins + 2 rows of
+ * RDN_REPORT_ROW_WORDS words.  Row 0 is the underflow bin (key < lo), rows 1 .. nbins the uniform bins
+ * of [lo, hi), row nbins + 1 the overflow bin (key >= hi, or a NaN key).  A row holds
+ * RDN_REPORT_QUANTITIES exact accumulators of RDN_ACC_STRIDE words each, in the order {MSE, SSIM,
+ * Smoothness, Peak2Peak, SNR_in, SNR_out, SNR_gain} and in the format of rdn_metrics_ex's accumulator
+ * (RDN_ACC_LIMBS limbs, then the count of values that were non-finite or >= 2^64 in magnitude), then word
+ * RDN_REPORT_COUNT, the number of spectra in the bin, and word RDN_REPORT_COUNT4, the number of those
+ * whose four metrics were supplied (per4): without per4 the first four accumulators and this count stay 0.
+ * Integer sums: a report's bits do not depend on the batch split, the atomics' order or the number of
+ * ranks whose reports are summed (all-reduce SUM over int64), for up to 2^31 spectra per report.
+ * Whole-set totals need no accumulator of their own: they are the word-wise sum of a report's rows
+ * (rdn_report_value's last row), so a caller who wants only totals passes nbins = 1 and any finite lo < hi.
+ *
+ * Bin of a key, evaluated in IEEE fp32 (every operation rounded to fp32, no fused multiply-add):
+ *   scale = (float)nbins / (hi - lo)
+ *   key is NaN  -> row nbins + 1;   key < lo -> row 0;   key >= hi -> row nbins + 1;   otherwise
+ *   i = (int)((key - lo) * scale)   truncated toward zero;   row = 1 + min(i, nbins - 1)
+ * (numpy: np.float32 scalars / arrays throughout, .astype(np.int32) for the truncation).
+ * rdn_report_bin evaluates it on the host. */
+#define RDN_REPORT_QUANTITIES 7
+#define RDN_REPORT_MAX_BINS 64
+#define RDN_REPORT_COUNT (RDN_REPORT_QUANTITIES * RDN_ACC_STRIDE)
+#define RDN_REPORT_COUNT4 (RDN_REPORT_COUNT + 1)
+#define RDN_REPORT_ROW_WORDS (RDN_REPORT_COUNT4 + 1)
+#define RDN_REPORT_ROWS(nbins) ((nbins) + 2)
+#define RDN_REPORT_WORDS(nbins) (RDN_REPORT_ROWS(nbins) * RDN_REPORT_ROW_WORDS)
+/* doubles per row of rdn_report_value: {count, sum MSE, SSIM, Smoothness, Peak2Peak, SNR_in, SNR_out,
+ * SNR_gain, count4} */
+#define RDN_REPORT_VALUES (RDN_REPORT_QUANTITIES + 2)
+
+/* One pass over x, y and clean ([n][L] device; clean fp32 or fp64 as rdn_metrics_ex takes it), L >= 1
+ * (L < 2^31: rows are addressed with 64-bit offsets, no 2^29 limit).  per_spectrum3: fp64 [n][3] device
+ * {SNR_in, SNR_out, SNR_gain} (may be NULL).  report: device, RDN_REPORT_WORDS(nbins) int64,
+ * ACCUMULATED (may be NULL; key, lo, hi, nbins and per4 are then not used and key / per4 must be NULL).
+ * With a report: 1 <= nbins <= RDN_REPORT_MAX_BINS, lo < hi both finite; key: fp32 [n] device, the value
+ * each spectrum is binned by (the nominal SNR of rdn_generate's snr_db or of a dataset), or NULL: the
+ * measured SNR_in rounded to fp32; per4: fp64 [n][4] device, the per-spectrum output of rdn_metrics_ex /
+ * rdn_forward_metrics for the same spectra, or NULL.  At least one of per_spectrum3 / report is needed. */
+int rdn_snr(const float* x, const float* y, const void* clean, int clean_is_f64, int64_t n, int64_t L,
+            double* per_spectrum3, const float* key, float lo, float hi, int nbins, const double* per4,
+            int64_t* report, void* stream);
+
+/* Host: the report row (0 .. nbins + 1) of `key` by the formula above. */
+int rdn_report_bin(float key, float lo, float hi, int nbins, int* row);
+
+/* Host: doubles of a HOST copy of a report.  out: (RDN_REPORT_ROWS(nbins) + 1) rows of RDN_REPORT_VALUES
+ * doubles: the report's rows in order, then the totals over all rows (their limbs added as integers).
+ * Each sum is the exact accumulated value rounded once to the nearest double, NaN for a quantity with an
+ * out-of-range value in that row (the contract of rdn_acc_value). */
+int rdn_report_value(const int64_t* report, int nbins, double* out);
+
 #ifdef __cplusplus
 }
 #endif
