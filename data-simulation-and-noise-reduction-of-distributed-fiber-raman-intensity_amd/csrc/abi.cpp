@@ -12,6 +12,7 @@
 #include "netspec.hpp"
 #include "host_util.hpp"
 #include "snr.hpp"
+#include "physics.hpp"
 
 namespace rdn {
 std::string pack(int arch, int dtype, const float* const* tensors, const int64_t* numels, int n, void* dst, size_t cap);
@@ -47,6 +48,8 @@ hipError_t launch_metrics(const float* y, const void* clean, bool clean_f64, int
                           long long* acc, hipStream_t s);
 hipError_t launch_snr(const float* x, const float* y, const void* clean, bool clean_f64, int64_t n, int L,
                       const snr::SnrOut& so, hipStream_t s);
+hipError_t launch_physics(const float* x, const float* y, const void* clean, bool clean_f64, int64_t n, int L,
+                          const phys::PhysOut& po, hipStream_t s);
 }  // namespace rdn
 
 namespace {
@@ -517,6 +520,50 @@ int rdn_report_value(const int64_t* report, int nbins, double* out) {
     for (int w = 0; w < RDN_REPORT_ROW_WORDS; ++w) total[w] = (int64_t)((uint64_t)total[w] + (uint64_t)r[w]);
   }
   values(total, out + (size_t)rows * RDN_REPORT_VALUES);
+  return RDN_OK;
+  RDN_GUARD_END
+}
+
+int rdn_physics(const float* x, const float* y, const void* clean, int clean_is_f64, int64_t n, int64_t L,
+                double alpha, double beta, double gamma, double* per_spectrum6, const float* key, float lo,
+                float hi, int nbins, int64_t* report, void* stream) {
+  RDN_GUARD_BEGIN
+  if (n > 0 && (!x || !y || !clean)) return fail(RDN_EINVAL, "rdn_physics: null pointer");
+  if (clean_is_f64 != 0 && clean_is_f64 != 1) return fail(RDN_EINVAL, "rdn_physics: clean_is_f64 must be 0 or 1");
+  if (n < 0 || L < 3 || L > 0x7fffffff) return fail(RDN_EINVAL, "rdn_physics: need n >= 0 and 3 <= L < 2^31");
+  if (!std::isfinite(alpha) || !std::isfinite(beta) || !std::isfinite(gamma))
+    return fail(RDN_EINVAL, "rdn_physics: the weights alpha, beta, gamma must be finite");
+  if (report && !valid_bins(lo, hi, nbins)) return fail(RDN_EINVAL, std::string("rdn_physics: ") + bins_msg());
+  if (!report && key) return fail(RDN_EINVAL, "rdn_physics: key feeds the report, which is NULL");
+  if (!report && !per_spectrum6) return fail(RDN_EINVAL, "rdn_physics: neither per_spectrum6 nor report to write");
+  if (n == 0) return RDN_OK;
+  const rdn::phys::PhysOut po{per_spectrum6, key, (long long*)report,
+                              report ? rdn::snr::make_bins(lo, hi, nbins) : rdn::snr::Bins{0.f, 0.f, 0.f, 0},
+                              alpha, beta, gamma};
+  return hip_check(rdn::launch_physics(x, y, clean, clean_is_f64 == 1, n, (int)L, po, (hipStream_t)stream), "physics");
+  RDN_GUARD_END
+}
+
+int rdn_physics_value(const int64_t* report, int nbins, double* out) {
+  RDN_GUARD_BEGIN
+  if (!report || !out) return fail(RDN_EINVAL, "rdn_physics_value: null pointer");
+  if (nbins < 1 || nbins > RDN_REPORT_MAX_BINS) return fail(RDN_EINVAL, "rdn_physics_value: need 1 <= nbins <= 64");
+  const int rows = RDN_REPORT_ROWS(nbins);
+  // the totals row: integer sums of the rows' words, added in unsigned arithmetic (rdn_report_value)
+  int64_t total[RDN_PHYS_ROW_WORDS] = {};
+  auto values = [](const int64_t* r, double* o) {
+    o[0] = (double)r[RDN_PHYS_COUNT];
+    for (int k = 0; k < RDN_PHYS_QUANTITIES; ++k) {
+      const int64_t* a = r + k * RDN_ACC_STRIDE;
+      o[1 + k] = a[RDN_ACC_LIMBS] ? std::nan("") : acc_to_double(a);
+    }
+  };
+  for (int b = 0; b < rows; ++b) {
+    const int64_t* r = report + (size_t)b * RDN_PHYS_ROW_WORDS;
+    values(r, out + (size_t)b * RDN_PHYS_VALUES);
+    for (int w = 0; w < RDN_PHYS_ROW_WORDS; ++w) total[w] = (int64_t)((uint64_t)total[w] + (uint64_t)r[w]);
+  }
+  values(total, out + (size_t)rows * RDN_PHYS_VALUES);
   return RDN_OK;
   RDN_GUARD_END
 }

@@ -9,7 +9,9 @@
 // blob_out.bin so that the test can compare it byte for byte with the library's own rdn_pack.
 // Then the error paths: wrong numel, too-small destination, null pointers, bad arch/dtype; and the
 // host side of the SNR report (rdn_snr's argument checks, rdn_report_bin, rdn_report_value on an
-// exactly-sized report).
+// exactly-sized report) and of the PhysicsAwareLoss report (rdn_physics's argument checks,
+// rdn_physics_value).
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -123,6 +125,40 @@ int main(int argc, char** argv) {
     EXPECT(val[(nb + 2) * RDN_REPORT_VALUES] == 2.0 && val[(nb + 2) * RDN_REPORT_VALUES + 5] == 1.0);
     EXPECT(rdn_report_value(rep.data(), 0, val.data()) == RDN_EINVAL);
     EXPECT(rdn_report_value(nullptr, nb, val.data()) == RDN_EINVAL);
+  }
+  // PhysicsAwareLoss report: argument checks (before any HIP call) and the host conversion of an
+  // exactly-sized report, an out-of-range word included
+  {
+    const int nb = 2;
+    std::vector<int64_t> rep(RDN_PHYS_WORDS(nb), 0);
+    std::vector<double> val((RDN_REPORT_ROWS(nb) + 1) * RDN_PHYS_VALUES, -1.0), per(6, 0.0);
+    const float* f = (const float*)rep.data();       // never read: every call below fails its checks or has n = 0
+    auto phys = [&](int64_t n, int64_t L, double a, double* per6, float lo, float hi, int nbins, int64_t* r) {
+      return rdn_physics(f, f, f, 0, n, L, a, 0.05, 0.01, per6, nullptr, lo, hi, nbins, r, nullptr);
+    };
+    EXPECT(phys(1, 2, 0.1, per.data(), 20.f, 37.f, nb, rep.data()) == RDN_EINVAL);            // L < 3
+    EXPECT(phys(1, 100, 0.1, per.data(), 20.f, 37.f, 65, rep.data()) == RDN_EINVAL);          // bad bins
+    EXPECT(phys(1, 100, 0.1, per.data(), 37.f, 20.f, nb, rep.data()) == RDN_EINVAL);
+    EXPECT(phys(1, 100, 0.1, nullptr, 20.f, 37.f, nb, nullptr) == RDN_EINVAL);                // nothing to write
+    EXPECT(phys(1, 100, std::nan(""), per.data(), 20.f, 37.f, nb, rep.data()) == RDN_EINVAL); // non-finite weight
+    EXPECT(rdn_physics(nullptr, nullptr, nullptr, 0, 1, 100, 0.1, 0.05, 0.01, per.data(), nullptr, 0.f, 0.f, 0, nullptr,
+                       nullptr) == RDN_EINVAL);
+    EXPECT(rdn_physics(nullptr, nullptr, nullptr, 0, 0, 100, 0.1, 0.05, 0.01, nullptr, nullptr, 20.f, 37.f, nb,
+                       rep.data(), nullptr) == RDN_OK);
+    // 2.25 in row 1's Total (quantity 4; limb 4 holds the units), 3 in row 2's PeakCount, and one
+    // out-of-range Peak (quantity 2) in row 2
+    int64_t* r1 = rep.data() + 1 * RDN_PHYS_ROW_WORDS;
+    int64_t* r2 = rep.data() + 2 * RDN_PHYS_ROW_WORDS;
+    r1[4 * RDN_ACC_STRIDE + 4] = 2, r1[4 * RDN_ACC_STRIDE + 3] = (int64_t)1 << 30, r1[RDN_PHYS_COUNT] = 1;
+    r2[4 * RDN_ACC_STRIDE + 3] = (int64_t)1 << 31, r2[5 * RDN_ACC_STRIDE + 4] = 3, r2[2 * RDN_ACC_STRIDE + RDN_ACC_LIMBS] = 1;
+    r2[RDN_PHYS_COUNT] = 2;
+    EXPECT(rdn_physics_value(rep.data(), nb, val.data()) == RDN_OK);
+    const double* t = val.data() + (nb + 2) * RDN_PHYS_VALUES;
+    EXPECT(val[1 * RDN_PHYS_VALUES + 5] == 2.25 && val[2 * RDN_PHYS_VALUES + 5] == 0.5 && val[2 * RDN_PHYS_VALUES + 6] == 3.0);
+    EXPECT(std::isnan(val[2 * RDN_PHYS_VALUES + 3]) && val[1 * RDN_PHYS_VALUES + 3] == 0.0);
+    EXPECT(t[0] == 3.0 && t[5] == 2.75 && t[6] == 3.0 && std::isnan(t[3]) && t[1] == 0.0);
+    EXPECT(rdn_physics_value(rep.data(), 0, val.data()) == RDN_EINVAL);
+    EXPECT(rdn_physics_value(nullptr, nb, val.data()) == RDN_EINVAL);
   }
 
   if (fails) return 1;

@@ -1,0 +1,139 @@
+// PhysicsAwareLoss on the device: one 512-thread workgroup per spectrum computes, in fp64, the four terms
+// of the loss PIDN and APIDN are trained against, their weighted total and the number of masked
+// positions, from the noisy input x, the denoised y and clean (definitions, report layout:
+// include/raman_mi355x.h rdn_physics; physics.hpp).  The reduction and the exact integer accumulators are
+// the metrics kernel's (metrics.hpp block_reduce / to_limbs), the bin formula is the SNR report's
+// (snr.hpp bin_row): a report's words are the same bits whatever the batch split, the atomics' order or
+// the number of ranks whose reports are summed.
+//
+// Reference: PIDN/train.py:109-146 (F.mse_loss, F.l1_loss of the first differences, the
+// torch.diff(clean, n=2) < 0 mask multiplied into both operands of an F.mse_loss over all L - 2 centre
+// positions, torch.var (unbiased) of noisy - clean and the mean of (noise^2 - var)^2).
+//
+// Passes.  The first reads x, y and clean (and the neighbours clean[p - 1], clean[p + 1], y[p + 1], which
+// the adjacent lanes load anyway: cache hits) and leaves mu = mean(x - clean); the variance about mu and
+// the noise term about the variance are two further passes over d = x - clean, which re-read x and clean
+// (the workgroup has just pulled them into L2).  Keeping d in registers instead (up to 32 doubles per
+// thread, a fully unrolled straight-line first pass) was built and measured: slower at every length
+// (DESIGN.md section 5), so there is one path for every L.  The neighbour indices are clamped into the row
+// and the terms that do not exist are selected away, so that no load sits behind a branch.
+//
+// Rows are addressed as pointer + 64-bit offset (no buffer descriptor), so any L < 2^31 runs.
+#include "metrics.hpp"
+#include "physics.hpp"
+
+namespace rdn {
+namespace phys {
+
+using met::MET_THREADS;
+
+template <typename TC>
+__global__ __launch_bounds__(MET_THREADS) void physics_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                              const TC* __restrict__ clean, int L, PhysOut po) {
+  __shared__ double red[MET_THREADS / 64];
+  const int tid = __builtin_amdgcn_workitem_id_x();
+  const int64_t n = __builtin_amdgcn_workgroup_id_x();
+  const float* xx = x + (size_t)n * L;
+  const float* yy = y + (size_t)n * L;
+  const TC* cc = clean + (size_t)n * L;
+  const auto add = [](double a, double b) { return a + b; };
+
+  // first pass.  A select, not a product, removes the terms that do not exist: a non-finite y at the
+  // row's end must not reach a sum it is not part of.
+  double se = 0.0, sm = 0.0, pk = 0.0, cnt = 0.0, sd = 0.0;
+#pragma unroll 4
+  for (int64_t p = tid; p < L; p += MET_THREADS) {
+    const bool has_next = p + 1 < L, inner = has_next && p >= 1;
+    const int64_t pn = has_next ? p + 1 : p, pm = p >= 1 ? p - 1 : p;
+    const TC c0 = cc[p], c1 = cc[pn], cm = cc[pm];
+    const double c = c0, a = yy[p], a1 = yy[pn];
+    const double d = (double)xx[p] - c;
+    se += (a - c) * (a - c);
+    sd += d;
+    const double s = fabs((a1 - a) - ((double)c1 - c));
+    sm += has_next ? s : 0.0;
+    // torch.diff(clean, n=2) < 0 in clean's own type: both first differences rounded to TC, then compared
+    const TC dn = c1 - c0, dp = c0 - cm;
+    const double m = dn < dp ? 1.0 : 0.0;
+    const double e = m * a - m * c;                  // pred * mask - clean * mask: NaN * 0 stays NaN
+    pk += inner ? e * e : 0.0;
+    cnt += inner ? m : 0.0;
+  }
+  se = met::block_reduce(se, red, add);
+  sm = met::block_reduce(sm, red, add);
+  pk = met::block_reduce(pk, red, add);
+  cnt = met::block_reduce(cnt, red, add);
+  sd = met::block_reduce(sd, red, add);
+
+  // unbiased variance of d in the centred two-pass form, then the mean of (d^2 - var)^2
+  const double mu = sd / L;
+  double sv = 0.0;
+#pragma unroll 4
+  for (int64_t p = tid; p < L; p += MET_THREADS) {
+    const double t = ((double)xx[p] - (double)cc[p]) - mu;
+    sv += t * t;
+  }
+  sv = met::block_reduce(sv, red, add);
+  const double var = sv / (L - 1);
+  double sq = 0.0;
+#pragma unroll 4
+  for (int64_t p = tid; p < L; p += MET_THREADS) {
+    const double d = (double)xx[p] - (double)cc[p];
+    const double q = d * d - var;
+    sq += q * q;
+  }
+  sq = met::block_reduce(sq, red, add);
+
+  const double mse = se / L, smooth = sm / (L - 1), peak = pk / (L - 2), noise = sq / L;
+  const double total = ((mse + po.alpha * smooth) + po.beta * peak) + po.gamma * noise;
+  const double v6[RDN_PHYS_QUANTITIES] = {mse, smooth, peak, noise, total, cnt};
+  if (tid == 0 && po.per6) {
+#pragma unroll
+    for (int k = 0; k < RDN_PHYS_QUANTITIES; ++k) po.per6[n * RDN_PHYS_QUANTITIES + k] = v6[k];
+  }
+  if (!po.report) return;
+
+  long long* row = po.report + (size_t)(po.key ? snr::bin_row(po.key[n], po.bins) : 1) * RDN_PHYS_ROW_WORDS;
+  // lanes 0..5 of wave 0 each own one quantity (integer atomics: order-free)
+  if (tid < RDN_PHYS_QUANTITIES) {
+    double v = v6[0];
+#pragma unroll
+    for (int k = 1; k < RDN_PHYS_QUANTITIES; ++k) v = tid == k ? v6[k] : v;
+    long long limb[RDN_ACC_LIMBS];
+    const bool ok = met::to_limbs(v, limb);
+    long long* a = row + tid * RDN_ACC_STRIDE;
+    if (ok) {
+#pragma unroll
+      for (int j = 0; j < RDN_ACC_LIMBS; ++j)
+        if (limb[j]) atomicAdd((unsigned long long*)&a[j], (unsigned long long)limb[j]);
+    } else {
+      atomicAdd((unsigned long long*)&a[RDN_ACC_LIMBS], 1ull);   // this quantity's out-of-range count
+    }
+  }
+  if (tid == 0) atomicAdd((unsigned long long*)&row[RDN_PHYS_COUNT], 1ull);
+}
+
+}  // namespace phys
+
+template <typename TC>
+static hipError_t launch_physics_t(const float* x, const float* y, const TC* clean, int64_t n, int L,
+                                   const phys::PhysOut& po, hipStream_t stream) {
+  const int64_t chunk = 0x7fffffff;
+  for (int64_t n0 = 0; n0 < n; n0 += chunk) {
+    const int64_t nn = n - n0 < chunk ? n - n0 : chunk;
+    phys::PhysOut c = po;
+    c.per6 = po.per6 ? po.per6 + n0 * RDN_PHYS_QUANTITIES : nullptr;
+    c.key = po.key ? po.key + n0 : nullptr;
+    hipLaunchKernelGGL(phys::physics_kernel<TC>, dim3((unsigned)nn), dim3(met::MET_THREADS), 0, stream, x + n0 * L,
+                       y + n0 * L, clean + n0 * L, L, c);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_physics(const float* x, const float* y, const void* clean, bool clean_f64, int64_t n, int L,
+                          const phys::PhysOut& po, hipStream_t stream) {
+  return clean_f64 ? launch_physics_t(x, y, (const double*)clean, n, L, po, stream)
+                   : launch_physics_t(x, y, (const float*)clean, n, L, po, stream);
+}
+
+}  // namespace rdn

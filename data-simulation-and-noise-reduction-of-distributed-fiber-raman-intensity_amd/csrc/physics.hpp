@@ -1,0 +1,23 @@
+// PhysicsAwareLoss report: what the host (abi.cpp) and the kernel (physics.hip) share -- the arguments
+// of a launch.  Definitions and report layout: include/raman_mi355x.h (rdn_physics).
+//
+// Reference: PIDN/train.py:109-146 (APIDN/train.py:162-199 is the same class): the loss PIDN and APIDN
+// are trained against, MSE + alpha * smoothness + beta * peak retention + gamma * noise model.
+#pragma once
+#include "common.hpp"
+#include "snr.hpp"
+
+namespace rdn {
+namespace phys {
+
+// where a launch's results go (per6 / report may be NULL; key only with a report)
+struct PhysOut {
+  double* per6;          // fp64 [n][6] {MSE, Smooth, Peak, Noise, Total, PeakCount}
+  const float* key;      // fp32 [n] binning key, NULL: every spectrum into row 1
+  long long* report;     // RDN_PHYS_WORDS(bins.nbins) int64, accumulated
+  snr::Bins bins;
+  double alpha, beta, gamma;
+};
+
+}  // namespace phys
+}  // namespace rdn

@@ -6,15 +6,18 @@ Drop-in surfaces (reference file:line):
   generate_signals                                数据集产生.py:5-64 (simulator.py, on-device)
   evaluate, compute_*                             */evaulate.py:14-39 (evaluate.py, batched, on-device)
   evaluate(..., snr_bins=), write_snr_report      SNR_in / SNR_out / gain and the metrics by SNR bin (engine.snr)
+  PhysicsAwareLoss                                PIDN|APIDN/train.py loss class (physics.py: value on device, gradient eager)
+  evaluate(..., physics=), write_physics_report   the loss's terms over a test set, by SNR bin (engine.physics)
 """
 from . import engine
 from ._lib import EngineError, RangeError
 from .dataset import load_dataset, save_dataset
 from .distributed import all_reduce_sums, shard
-from .evaluate import evaluate, write_metrics, write_snr_report
+from .evaluate import evaluate, write_metrics, write_physics_report, write_snr_report
 from .models import ADSDN, APIDN, DSDN, MODELS, PIDN, DenoiseCNN, RRCDNet
+from .physics import PhysicsAwareLoss
 from .simulator import generate, generate_signals
 
 __all__ = ["engine", "DenoiseCNN", "RRCDNet", "DSDN", "ADSDN", "PIDN", "APIDN", "MODELS", "generate",
            "generate_signals", "evaluate", "write_metrics", "write_snr_report", "load_dataset", "save_dataset", "shard",
-           "all_reduce_sums", "EngineError", "RangeError"]
+           "all_reduce_sums", "EngineError", "RangeError", "PhysicsAwareLoss", "write_physics_report"]

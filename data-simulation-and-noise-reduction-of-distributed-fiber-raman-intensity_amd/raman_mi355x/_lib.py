@@ -42,6 +42,17 @@ def report_words(nbins):
     return report_rows(nbins) * REPORT_ROW_WORDS
 
 
+# PhysicsAwareLoss report words (include/raman_mi355x.h RDN_PHYS_*)
+PHYS_QUANTITIES = 6
+PHYS_COUNT = PHYS_QUANTITIES * ACC_STRIDE
+PHYS_ROW_WORDS = PHYS_COUNT + 1
+PHYS_VALUES = PHYS_QUANTITIES + 1
+
+
+def phys_words(nbins):
+    return report_rows(nbins) * PHYS_ROW_WORDS
+
+
 def source_hash():
     """sha256 prefix of the sources the library is built from -- the same files, in the same order,
     as csrc/Makefile's STAMP_SRC (None when the sources are not beside the package)."""
@@ -105,6 +116,11 @@ _SIGNATURES = {
     "rdn_report_bin": ([ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.POINTER(ctypes.c_int)],
                        ctypes.c_int),
     "rdn_report_value": ([ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+    # the PhysicsAwareLoss report: likewise added to ABI v6 and detected by symbol
+    "rdn_physics": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                     ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
+                     ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rdn_physics_value": ([ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGNATURES)

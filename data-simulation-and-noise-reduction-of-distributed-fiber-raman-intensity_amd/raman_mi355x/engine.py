@@ -543,3 +543,91 @@ def snr(x, y, clean, key=None, bins=None, per4=None, report=None, per_spectrum=T
     _lib.check(_lib.lib().rdn_snr(ptr(x), ptr(y), ptr(clean), int(clean.dtype == torch.float64), n, L, ptr(per),
                                   ptr(key), lo, hi, nbins, ptr(per4), ptr(report), _stream(dev)), "rdn_snr")
     return per, report
+
+
+# ---- PhysicsAwareLoss report (rdn_physics; definitions and report layout: include/raman_mi355x.h) ----
+PHYS_QUANTITIES = ("MSE", "Smooth", "Peak", "Noise", "Total", "PeakCount")
+PHYS_WEIGHTS = (0.1, 0.05, 0.01)          # PIDN/train.py:112 alpha, beta, gamma
+
+
+def _weights(weights):
+    """(alpha, beta, gamma) as rdn_physics takes them: three finite floats."""
+    try:
+        a, b, g = (float(w) for w in weights)
+    except (TypeError, ValueError):
+        raise ValueError(f"weights must be (alpha, beta, gamma), got {weights!r}") from None
+    if not all(abs(w) < float("inf") for w in (a, b, g)):          # NaN fails the comparison too
+        raise ValueError(f"weights must be finite, got {(a, b, g)}")
+    return a, b, g
+
+
+def new_physics_report(nbins, device):
+    """A zeroed PhysicsAwareLoss report (RDN_PHYS_WORDS(nbins) int64: nbins + 2 rows) on ``device``."""
+    if isinstance(nbins, bool) or int(nbins) != nbins or not 1 <= int(nbins) <= _lib.REPORT_MAX_BINS:
+        raise ValueError(f"nbins must be an integer in [1, {_lib.REPORT_MAX_BINS}], got {nbins!r}")
+    return torch.zeros(_lib.phys_words(int(nbins)), dtype=torch.int64, device=device)
+
+
+def physics_value(report, nbins):
+    """Doubles of a PhysicsAwareLoss report (float64 (nbins + 3, 7), CPU): one row per report row --
+    underflow, the bins, overflow -- then the totals over all of them; columns {count, ΣMSE, ΣSmooth, ΣPeak,
+    ΣNoise, ΣTotal, ΣPeakCount}.  Each sum is the exact total rounded once, NaN where a value was out of
+    range (rdn_physics_value)."""
+    nbins = int(nbins)
+    if not 1 <= nbins <= _lib.REPORT_MAX_BINS:
+        raise ValueError(f"nbins must be in [1, {_lib.REPORT_MAX_BINS}], got {nbins}")
+    h = report.detach().to("cpu", torch.int64).contiguous()
+    if h.numel() != _lib.phys_words(nbins):
+        raise ValueError(f"a physics report of {nbins} bins has {_lib.phys_words(nbins)} words, got {h.numel()}")
+    out = torch.empty((_lib.report_rows(nbins) + 1, _lib.PHYS_VALUES), dtype=torch.float64)
+    _lib.check(_lib.lib().rdn_physics_value(ctypes.cast(h.data_ptr(), ctypes.POINTER(ctypes.c_int64)), nbins,
+                                            ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_double))),
+               "rdn_physics_value")
+    return out
+
+
+def physics(x, y, clean, weights=PHYS_WEIGHTS, key=None, bins=None, report=None, per_spectrum=True):
+    """Per-spectrum [MSE, Smooth, Peak, Noise, Total, PeakCount] (fp64, (n, 6)) of PhysicsAwareLoss
+    (PIDN/train.py:109-146) for the denoised ``y`` and the noisy input ``x`` (float32) against ``clean``
+    (float32 or float64), Total weighted by ``weights`` = (alpha, beta, gamma); the reference's loss over
+    the batch is the mean of Total.  With ``bins`` = (lo, hi, nbins) the batch is also added to a report
+    binned by ``key`` (float32 (n,), e.g. the nominal or measured SNR; None puts every spectrum into row 1:
+    an unbinned report is bins=(0, 1, 1) without a key).  ``report``: a report of
+    new_physics_report(nbins) to accumulate into (made when None).  Returns (per (n, 6) or None, report or
+    None)."""
+    _check_cuda_f32(x, "input")
+    _check_cuda_f32(y, "denoised")
+    if not (torch.is_tensor(clean) and clean.is_cuda):
+        raise RuntimeError("raman_mi355x runs on the GPU only: clean must be a CUDA (HIP) tensor")
+    if clean.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"clean must be float32 or float64, got {clean.dtype}")
+    alpha, beta, gamma = _weights(weights)
+    x, y, clean = _rows(x), _rows(y), _rows(clean)
+    if x.shape != y.shape or y.shape != clean.shape:
+        raise ValueError(f"shape mismatch {tuple(x.shape)} vs {tuple(y.shape)} vs {tuple(clean.shape)}")
+    n, L = y.shape
+    if L < 3:
+        raise ValueError("spectra must have at least three samples (the peak term is a mean over L - 2)")
+    dev = y.device
+    if x.device != dev or clean.device != dev:
+        raise ValueError(f"denoised on {dev} but input on {x.device} and clean on {clean.device}")
+    if bins is None:
+        if key is not None or report is not None:
+            raise ValueError("key and report belong to the binned report: pass bins=(lo, hi, nbins)")
+        if not per_spectrum:
+            raise ValueError("nothing to compute: per_spectrum=False and no bins")
+        lo = hi = 0.0
+        nbins = 0
+    else:
+        lo, hi, nbins = _bins(bins)
+        if report is None:
+            report = new_physics_report(nbins, dev)
+        else:
+            _check_out(report, "report", (_lib.phys_words(nbins),), dev, torch.int64)
+        if key is not None:
+            _check_out(key, "key", (n,), dev, torch.float32)
+    per = torch.empty((n, 6), dtype=torch.float64, device=dev) if per_spectrum else None
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+    _lib.check(_lib.lib().rdn_physics(ptr(x), ptr(y), ptr(clean), int(clean.dtype == torch.float64), n, L, alpha, beta,
+                                      gamma, ptr(per), ptr(key), lo, hi, nbins, ptr(report), _stream(dev)), "rdn_physics")
+    return per, report

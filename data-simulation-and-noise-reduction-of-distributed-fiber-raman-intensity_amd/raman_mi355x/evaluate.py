@@ -92,6 +92,52 @@ def snr_summary(report, bins):
     return out
 
 
+PHYS_KEYS = engine.PHYS_QUANTITIES
+# keys of a result that write_metrics leaves to write_snr_report / write_physics_report
+_EXTRA_RESULT_KEYS = _SNR_RESULT_KEYS + ("physics",)
+
+
+def _physics_weights(physics):
+    """``physics`` of evaluate(): None / False -> None, True -> the reference's default weights,
+    (alpha, beta, gamma) -> those."""
+    if physics is None or physics is False:
+        return None
+    return engine._weights(engine.PHYS_WEIGHTS if physics is True else physics)
+
+
+def physics_summary(report, weights, L, bins=None):
+    """The ``"physics"`` entry of a result, from an (all-reduced) PhysicsAwareLoss report of spectra of
+    length ``L``: the ``weights``, the ``count`` of spectra, the means of MSE, Smooth, Peak, Noise, Total
+    and PeakCount over all of them (the mean of Total is the reference's loss over the whole set, each
+    term's mean the reference's term), and ``PeakMasked`` = ΣPeak (L - 2) / ΣPeakCount, the squared error
+    per masked position (Peak itself is a mean over all L - 2 positions; NaN when nothing is masked).
+    With ``bins`` = (lo, hi, nbins): ``by_snr``, one such entry per bin with its edges ``lo`` / ``hi``
+    (the means only where the bin is not empty), and ``under`` / ``over`` for keys below ``lo`` and at or
+    above ``hi`` (or NaN).  A mean over values that include a non-finite one is NaN."""
+    nbins = engine._bins(bins)[2] if bins is not None else 1
+    v = engine.physics_value(report, nbins).tolist()
+
+    def entry(row, head):
+        count = int(row[0])
+        e = dict(head, count=count)
+        if count > 0:
+            for i, k in enumerate(PHYS_KEYS):
+                e[k] = row[1 + i] / count
+            e["PeakMasked"] = row[3] * (L - 2) / row[6] if row[6] > 0 else float("nan")
+        return e
+
+    out = entry(v[nbins + 2], {"weights": list(weights)})
+    if out["count"] <= 0:
+        raise ValueError("no spectra were evaluated")
+    if bins is not None:
+        lo, hi, _ = engine._bins(bins)
+        edges = np.linspace(np.float64(lo), np.float64(hi), nbins + 1).tolist()
+        out["by_snr"] = [entry(v[1 + b], {"lo": edges[b], "hi": edges[b + 1]}) for b in range(nbins)]
+        out["under"] = entry(v[0], {"lo": float("-inf"), "hi": lo})
+        out["over"] = entry(v[nbins + 1], {"lo": hi, "hi": float("inf")})
+    return out
+
+
 def _engine_module(model):
     """A raman_mi355x network whose own forward is the engine (not a subclass overriding forward)."""
     from .models import _EngineNet
@@ -116,7 +162,7 @@ def _workspace(model, n, L, device):
     return engine.Workspace(model.ARCH, model.engine_code, n, L, device)
 
 
-def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bins=None, snrs=None):
+def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bins=None, snrs=None, physics=None):
     """evaulate.py:25-39 batched on the device.  Inputs beyond the 16-bit modes' domain (|x| > 4) or
     activations beyond the e4m3 planes' range raise RangeError after the run (one check at the end,
     no per-batch wait) -- unlike the module's own forward, which re-runs such a batch in fp32: evaluate
@@ -125,7 +171,12 @@ def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bi
     ``snr_bins`` = (lo, hi, nbins) additionally runs the SNR pass on every batch (engine.snr) and adds
     snr_summary's keys to the result: the mean SNR_in, SNR_out and SNR_gain in dB and ``by_snr``, the
     seven means per bin of ``snrs`` -- the dataset's nominal SNR per spectrum (the ``snrs`` array of a
-    test.npz), or, when None, the measured SNR_in.  The report is all-reduced like the accumulator."""
+    test.npz), or, when None, the measured SNR_in.  The report is all-reduced like the accumulator.
+
+    ``physics`` = True (the reference's weights 0.1, 0.05, 0.01) or (alpha, beta, gamma) additionally runs
+    the PhysicsAwareLoss pass on every batch (engine.physics) and adds one key, ``"physics"``
+    (physics_summary): the terms PIDN / APIDN were trained against, their weighted total and -- with
+    ``snr_bins`` -- the same per bin of the key the SNR report bins by."""
     model.eval()
     if device is None:
         device = next(model.parameters()).device
@@ -149,6 +200,9 @@ def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bi
                 raise ValueError(f"snrs has {snrs.numel()} values for {noisy.shape[0]} spectra")
     elif snrs is not None:
         raise ValueError("snrs is the binning key of the SNR report: pass snr_bins=(lo, hi, nbins)")
+    weights = _physics_weights(physics)
+    phys_bins = snr_bins if snr_bins is not None else (0.0, 1.0, 1)      # unbinned: one bin, no key
+    phys_rep = engine.new_physics_report(engine._bins(phys_bins)[2], device) if weights is not None else None
     ws = _workspace(model, min(batch_size, max(hi - lo, 1)), L, device)
     # fp64 clean stays fp64 (the metrics compare against the same float64 values as evaulate.py)
     cdt = torch.float64 if (clean.dtype == torch.float64 if torch.is_tensor(clean) else clean.dtype == np.float64) \
@@ -167,17 +221,28 @@ def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bi
                 per, _ = engine.metrics(y.squeeze(1), c, per_spectrum=report is not None, acc=acc)
             if report is not None:
                 key = snrs[b0:b1].to(device) if snrs is not None else None
-                engine.snr(x, y, c, key=key, bins=snr_bins, per4=per, report=report, per_spectrum=False)
+                # without nominal SNRs the physics report needs the key rdn_snr bins by: its SNR_in in fp32
+                per3, _ = engine.snr(x, y, c, key=key, bins=snr_bins, per4=per, report=report,
+                                     per_spectrum=phys_rep is not None and key is None)
+                if per3 is not None:
+                    key = per3[:, 0].to(torch.float32).contiguous()
+            else:
+                key = None
+            if phys_rep is not None:
+                engine.physics(x, y, c, weights=weights, key=key, bins=phys_bins, report=phys_rep, per_spectrum=False)
     _finish(model, ws)
     _all_reduce_acc(acc)
     means = means_from_acc(acc)
     if report is not None:
         means.update(snr_summary(_all_reduce_acc(report), snr_bins))
+    if phys_rep is not None:
+        means["physics"] = physics_summary(_all_reduce_acc(phys_rep), weights, L, snr_bins)
     return means
 
 
 def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_size=8192, device=None,
-                       first_index=0, gen_kwargs=None, log_every_s=0.0, fused_metrics=True, snr_bins=None):
+                       first_index=0, gen_kwargs=None, log_every_s=0.0, fused_metrics=True, snr_bins=None,
+                       physics=None):
     """Config 4: ``total`` simulator spectra [first_index, first_index + total),
     sharded over the ranks as [r·N/W, (r+1)·N/W), each chunk generated on the device, denoised by
     every model in ``models`` (name -> module) and metered into that model's exact accumulator.
@@ -189,11 +254,16 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
     ``snr_bins`` = (lo, hi, nbins) additionally runs the SNR pass on every chunk, binned by the
     generator's nominal SNR (its ``snr_db``), and adds snr_summary's keys (SNR_in, SNR_out, SNR_gain,
     by_snr, ...) and the all-reduced ``report`` words to each model's entry -- the same bits for any world
-    size or batch size, like the means."""
+    size or batch size, like the means.
+    ``physics`` = True or (alpha, beta, gamma) additionally runs the PhysicsAwareLoss pass on every chunk
+    (binned by the nominal SNR when ``snr_bins`` is given) and adds ``"physics"`` (physics_summary, with
+    the all-reduced ``report`` words) to each model's entry -- exact accumulators, the same bits likewise."""
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
     gen_kwargs = gen_kwargs or {}
+    weights = _physics_weights(physics)
+    phys_bins = snr_bins if snr_bins is not None else (0.0, 1.0, 1)
     rank, W = world()
     lo, hi = shard(total, rank, W)
     L = int(signal_length)
@@ -207,6 +277,7 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
             model.eval()
             acc = engine.new_acc(device)
             report = engine.new_report(engine._bins(snr_bins)[2], device) if snr_bins is not None else None
+            phys_rep = engine.new_physics_report(engine._bins(phys_bins)[2], device) if weights is not None else None
             ws = _workspace(model, B, L, device)
             packed = model.packed_weights(device)
             if dist.is_available() and dist.is_initialized():
@@ -237,6 +308,10 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
                 if report is not None:
                     engine.snr(noisy[:nb], y[:nb], clean[:nb], key=snr_db, bins=snr_bins, per4=per, report=report,
                                per_spectrum=False)
+                if phys_rep is not None:
+                    engine.physics(noisy[:nb], y[:nb], clean[:nb], weights=weights,
+                                   key=snr_db if snr_bins is not None else None, bins=phys_bins, report=phys_rep,
+                                   per_spectrum=False)
             _finish(model, ws)              # waits for the stream; raises on a timed-out hand-off / range / gate
             torch.cuda.synchronize(device)
             el = time.perf_counter() - t0
@@ -253,16 +328,21 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
                 _all_reduce_acc(report)
                 out[name].update(snr_summary(report, snr_bins))
                 out[name]["report"] = report.cpu().tolist()
+            if phys_rep is not None:
+                _all_reduce_acc(phys_rep)
+                out[name]["physics"] = physics_summary(phys_rep, weights, L, snr_bins)
+                out[name]["physics"]["report"] = phys_rep.cpu().tolist()
     return out
 
 
 def write_metrics(metrics, root="eval_results"):
-    """evaulate.py:78-80's metrics.txt; what ``snr_bins`` added to a result goes to write_snr_report."""
+    """evaulate.py:78-80's metrics.txt; what ``snr_bins`` / ``physics`` added to a result goes to
+    write_snr_report / write_physics_report."""
     save_dir = os.path.join(root, datetime.now().strftime("%Y%m%d_%H%M%S"))
     os.makedirs(save_dir, exist_ok=True)
     with open(os.path.join(save_dir, "metrics.txt"), "w") as f:
         for k, v in metrics.items():
-            if k not in _SNR_RESULT_KEYS:
+            if k not in _EXTRA_RESULT_KEYS:
                 f.write(f"{k}: {v:.6f}\n")
     return save_dir
 
@@ -286,4 +366,29 @@ def write_snr_report(result, root):
         for e in [result["snr_under"]] + list(result["by_snr"]) + [result["snr_over"]]:
             f.write(f"{e['lo']:.4f} {e['hi']:.4f} {e['count']} "
                     + " ".join(f"{e[k]:.6f}" if k in e else "-" for k in cols) + "\n")
+    return root
+
+
+def write_physics_report(result, root):
+    """Write the ``"physics"`` entry of an ``evaluate(..., physics=...)`` result into the directory ``root``
+    (e.g. the one write_metrics returned): ``physics_report.json`` (the entry as it is) and
+    ``physics_report.txt`` -- the weights, the means, and with ``snr_bins`` a table with one line per bin."""
+    import json
+    if "physics" not in result:
+        raise ValueError("the result has no physics report: evaluate with physics=True or (alpha, beta, gamma)")
+    os.makedirs(root, exist_ok=True)
+    part = result["physics"]
+    with open(os.path.join(root, "physics_report.json"), "w") as f:
+        json.dump(part, f, indent=1)
+    cols = PHYS_KEYS + ("PeakMasked",)
+    with open(os.path.join(root, "physics_report.txt"), "w") as f:
+        f.write("weights: " + " ".join(f"{w:g}" for w in part["weights"]) + "\n")
+        f.write(f"count: {part['count']}\n")
+        for k in cols:
+            f.write(f"{k}: {part[k]:.6e}\n")
+        if "by_snr" in part:
+            f.write("lo hi count " + " ".join(cols) + "\n")
+            for e in [part["under"]] + list(part["by_snr"]) + [part["over"]]:
+                f.write(f"{e['lo']:.4f} {e['hi']:.4f} {e['count']} "
+                        + " ".join(f"{e[k]:.6e}" if k in e else "-" for k in cols) + "\n")
     return root

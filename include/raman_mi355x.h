@@ -308,6 +308,58 @@ int rdn_report_bin(float key, float lo, float hi, int nbins, int* row);
  * out-of-range value in that row (the contract of rdn_acc_value). */
 int rdn_report_value(const int64_t* report, int nbins, double* out);
 
+/* ---- PhysicsAwareLoss report (added to ABI v6 without a version bump: detect the entry points by symbol)
+ *
+ * The forward value of the loss PIDN and APIDN are trained against (PIDN/train.py:109-146), per spectrum.
+ * With p the denoised output (fp32), c clean (fp32 / fp64) and x the noisy input (fp32), i = 0 .. L-1, all
+ * arithmetic in fp64 on the stored values except the mask:
+ *   MSE    = sum_i (p_i - c_i)^2 / L
+ *   Smooth = sum_{i < L-1} |(p_{i+1} - p_i) - (c_{i+1} - c_i)| / (L - 1)
+ *   m_i    = 1 if (c_{i+1} - c_i) < (c_i - c_{i-1}) else 0,  i = 1 .. L-2; both differences are formed and
+ *            compared in clean's own storage type (fp32 arithmetic for fp32 clean, fp64 for fp64 clean):
+ *            torch.diff(clean, n=2) < 0.  NaN compares false.
+ *   PeakCount = sum_i m_i
+ *   Peak   = sum_{i=1}^{L-2} (m_i p_i - m_i c_i)^2 / (L - 2)     the mean over ALL L - 2 positions; m_i is a
+ *            factor, not a select: a non-finite p at an unmasked position gives NaN, as the reference does
+ *   d_i = x_i - c_i;  mu = sum_i d_i / L;  v = sum_i (d_i - mu)^2 / (L - 1)   (unbiased, centred two-pass)
+ *   Noise  = sum_i (d_i^2 - v)^2 / L
+ *   Total  = ((MSE + alpha Smooth) + beta Peak) + gamma Noise      reference defaults 0.1, 0.05, 0.01
+ * All spectra of a call share one L, so the reference's loss over a batch is the mean of Total over its
+ * spectra (and each of its terms the mean of the per-spectrum term).  Non-finite values are written as
+ * they are to the per-spectrum output and counted in the quantity's out-of-range word in a report: never
+ * clamped.
+ *
+ * Report: RDN_PHYS_WORDS(nbins) int64 on the device, RDN_REPORT_ROWS(nbins) rows of RDN_PHYS_ROW_WORDS
+ * words with the row structure and bin formula of the SNR report above (row 0 underflow, rows 1 .. nbins
+ * the uniform bins of [lo, hi), row nbins + 1 overflow / NaN key).  A row holds RDN_PHYS_QUANTITIES exact
+ * accumulators of RDN_ACC_STRIDE words in the order {MSE, Smooth, Peak, Noise, Total, PeakCount}, in
+ * rdn_metrics_ex's limb format, then word RDN_PHYS_COUNT, the number of spectra in the row.  Integer
+ * sums: the same bits for any batch split, atomics order or number of ranks. */
+#define RDN_PHYS_QUANTITIES 6
+#define RDN_PHYS_COUNT (RDN_PHYS_QUANTITIES * RDN_ACC_STRIDE)
+#define RDN_PHYS_ROW_WORDS (RDN_PHYS_COUNT + 1)
+#define RDN_PHYS_WORDS(nbins) (RDN_REPORT_ROWS(nbins) * RDN_PHYS_ROW_WORDS)
+/* doubles per row of rdn_physics_value: {count, sum MSE, Smooth, Peak, Noise, Total, PeakCount} */
+#define RDN_PHYS_VALUES (RDN_PHYS_QUANTITIES + 1)
+
+/* x, y, clean: [n][L] device (clean fp32 or fp64 as rdn_metrics_ex takes it), 3 <= L < 2^31 (rows are
+ * addressed with 64-bit offsets).  alpha, beta, gamma: the weights of Total, finite.  per_spectrum6: fp64
+ * [n][6] device, the six quantities in the order above (may be NULL).  report: device,
+ * RDN_PHYS_WORDS(nbins) int64, ACCUMULATED (may be NULL; key, lo, hi and nbins are then not used and key
+ * must be NULL).  With a report: 1 <= nbins <= RDN_REPORT_MAX_BINS, lo < hi both finite; key: fp32 [n]
+ * device, the value each spectrum is binned by, or NULL: every spectrum goes into row 1 (an unbinned
+ * report: nbins = 1 and any finite lo < hi).  At least one of per_spectrum6 / report is needed.  n = 0
+ * launches nothing and accepts NULL data pointers. */
+int rdn_physics(const float* x, const float* y, const void* clean, int clean_is_f64, int64_t n, int64_t L,
+                double alpha, double beta, double gamma, double* per_spectrum6, const float* key, float lo,
+                float hi, int nbins, int64_t* report, void* stream);
+
+/* Host: doubles of a HOST copy of a report of rdn_physics.  out: (RDN_REPORT_ROWS(nbins) + 1) rows of
+ * RDN_PHYS_VALUES doubles: the report's rows in order, then the totals over all rows (their limbs added as
+ * integers).  Each sum is the exact accumulated value rounded once to the nearest double, NaN for a
+ * quantity with an out-of-range value in that row (the contract of rdn_acc_value). */
+int rdn_physics_value(const int64_t* report, int nbins, double* out);
+
 #ifdef __cplusplus
 }
 #endif
