@@ -385,6 +385,11 @@ int rdn_generate(uint64_t seed, uint64_t first_index, int64_t n, const rdn_gen_p
   if (!p || (n > 0 && (!clean || !noisy))) return fail(RDN_EINVAL, "rdn_generate: null pointer");
   if (n < 0 || p->signal_length < 1 || p->signal_length > 0x7fffffff || p->max_repeat < 1 || !(p->snr_hi >= p->snr_lo))
     return fail(RDN_EINVAL, "rdn_generate: bad parameters");
+  // the kernel scans 256 segment lengths per pass in int: a pass starts below L and adds at most 256 * max_repeat
+  if (p->signal_length + 256 * (int64_t)p->max_repeat > 0x7fffffff)
+    return fail(RDN_EINVAL, "rdn_generate: signal_length + 256 * max_repeat exceeds INT32_MAX");
+  if (!std::isfinite(p->snr_lo) || !std::isfinite(p->snr_hi) || std::isnan(p->extreme_noise_prob))
+    return fail(RDN_EINVAL, "rdn_generate: non-finite snr_lo / snr_hi or NaN extreme_noise_prob");
   if (n == 0) return RDN_OK;
   return hip_check(rdn::launch_generate(seed, first_index, n, (int)p->signal_length, p->snr_lo, p->snr_hi,
                                         p->extreme_noise_prob, p->max_repeat, clean, noisy, snr_db, noise_std,

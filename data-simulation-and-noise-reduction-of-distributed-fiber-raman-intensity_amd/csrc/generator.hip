@@ -93,6 +93,8 @@ __global__ __launch_bounds__(GT) void generate_kernel(uint64_t seed, uint64_t fi
   float* nz = noisy + (size_t)__builtin_amdgcn_workgroup_id_x() * L;
 
   // ---- phase A: piecewise-constant segments (raw values into `clean`) --------------------------
+  // pos < L when a pass starts and the pass adds at most GT * max_repeat: rdn_generate admits only
+  // L + 256 * max_repeat <= INT32_MAX, so neither the scan nor pos leaves int
   float mn = INFINITY, mx = -INFINITY;
   int pos = 0;
   for (int kb = 0; pos < L; kb += GT) {

@@ -7,11 +7,13 @@
 // tensors.bin: for each name of rdn_param_names(arch), in order: int64 numel, then numel float32
 // (written by tests/test_abi.py::test_host_sanitizer_pack).  The packed blob is written to
 // blob_out.bin so that the test can compare it byte for byte with the library's own rdn_pack.
-// Then the error paths: wrong numel, too-small destination, null pointers, bad arch/dtype; and the
+// Then the error paths: wrong numel, too-small destination, null pointers, bad arch/dtype, the
+// simulator's parameter bounds (rdn_generate with n = 0); and the
 // host side of the SNR report (rdn_snr's argument checks, rdn_report_bin, rdn_report_value on an
 // exactly-sized report) and of the PhysicsAwareLoss report (rdn_physics's argument checks,
 // rdn_physics_value).
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -97,6 +99,25 @@ int main(int argc, char** argv) {
                      nullptr) == RDN_EINVAL);
   EXPECT(rdn_metrics(nullptr, nullptr, 1, 100, nullptr, nullptr, nullptr) == RDN_EINVAL);
   EXPECT(rdn_generate(0, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == RDN_EINVAL);
+  // simulator parameters, n = 0 (nothing touches the device): the 32-bit scan bound at both ends, non-finite floats
+  {
+    auto gen = [](int64_t L, float lo, float hi, float prob, int32_t max_repeat) {
+      const rdn_gen_params p{L, lo, hi, prob, max_repeat};
+      return rdn_generate(~0ull, ~0ull, 0, &p, nullptr, nullptr, nullptr, nullptr, nullptr);
+    };
+    const float inf = INFINITY, nan = NAN;
+    EXPECT(gen(1000, 20.f, 37.f, 0.05f, 8388604) == RDN_OK);
+    EXPECT(gen(1000, 20.f, 37.f, 0.05f, 8388605) == RDN_EINVAL);
+    EXPECT(gen(1000, 20.f, 37.f, 0.05f, INT32_MAX) == RDN_EINVAL);
+    EXPECT(gen(1000, 20.f, 37.f, 0.05f, INT32_MIN) == RDN_EINVAL);
+    EXPECT(gen(INT32_MAX, 20.f, 37.f, 0.05f, 1) == RDN_EINVAL);
+    EXPECT(gen(INT64_MAX, 20.f, 37.f, 0.05f, INT32_MAX) == RDN_EINVAL);
+    EXPECT(gen(INT32_MAX - 256, 5.f, 5.f, 1.f, 1) == RDN_OK);
+    EXPECT(gen(1000, nan, 37.f, 0.05f, 40) == RDN_EINVAL);
+    EXPECT(gen(1000, 20.f, inf, 0.05f, 40) == RDN_EINVAL);
+    EXPECT(gen(1000, -inf, 37.f, 0.05f, 40) == RDN_EINVAL);
+    EXPECT(gen(1000, 20.f, 37.f, nan, 40) == RDN_EINVAL);
+  }
   // SNR report: argument checks, the bin formula and the host conversion of an exactly-sized report
   {
     const int nb = 3;

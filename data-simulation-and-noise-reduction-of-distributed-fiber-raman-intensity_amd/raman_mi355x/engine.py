@@ -5,6 +5,7 @@ check shapes/devices, allocate outputs through the PyTorch caching allocator and
 pointers.  Nothing here has a CPU or PyTorch-op fallback.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -365,13 +366,46 @@ def forward_metrics(arch, dtype, packed, x, clean, out=None, sums=None, per_spec
     return y, per, sums, bool(fused.value)
 
 
+GEN_SCAN = 256                 # segment lengths the simulator sums per pass, in int32 (generator.hip phase A)
+_INT32_MAX = 2 ** 31 - 1
+
+
+def check_generate_args(n, seed, first_index, signal_length, snr_range, extreme_noise_prob, max_repeat):
+    """ValueError for what rdn_generate refuses (include/raman_mi355x.h) and for a seed or index that
+    ctypes would wrap into uint64 silently; returns the values as the ABI takes them.  Needs no device."""
+    n, seed, first, L, mr = int(n), int(seed), int(first_index), int(signal_length), int(max_repeat)
+    if n < 0:
+        raise ValueError(f"n must be >= 0, got {n}")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must be in [0, 2^64), got {seed}")
+    if not 0 <= first < 2 ** 64:
+        raise ValueError(f"first_index must be in [0, 2^64), got {first}")
+    if first + n > 2 ** 64:
+        raise ValueError(f"first_index + n = {first + n} passes 2^64: the 64-bit spectrum index would wrap onto 0")
+    if not 1 <= L <= _INT32_MAX:
+        raise ValueError(f"signal_length must be in [1, 2^31), got {L}")
+    if mr < 1 or L + GEN_SCAN * mr > _INT32_MAX:
+        raise ValueError(f"max_repeat must be >= 1 with signal_length + {GEN_SCAN} * max_repeat <= {_INT32_MAX} "
+                         f"(at most {(_INT32_MAX - L) // GEN_SCAN} here), got {mr}")
+    lo, hi, prob = (ctypes.c_float(float(v)).value for v in (snr_range[0], snr_range[1], extreme_noise_prob))
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+        raise ValueError(f"snr_range must be finite in float32 with lo <= hi, got {tuple(snr_range)}")
+    if math.isnan(prob):
+        raise ValueError("extreme_noise_prob must not be NaN")
+    return n, seed, first, L, lo, hi, prob, mr
+
+
 def generate(n, seed, first_index=0, signal_length=10000, snr_range=(20.0, 37.0), extreme_noise_prob=0.05,
              max_repeat=40, device="cuda", out=None):
-    """Device simulator (数据集产生.py:5-64 contract): returns clean, noisy (n, L), snr, noise_std (n,)."""
+    """Device simulator (数据集产生.py:5-64 contract): returns clean, noisy (n, L), snr, noise_std (n,).
+
+    ``seed`` and ``first_index`` are unsigned 64-bit with first_index + n <= 2^64; out-of-range values and
+    the parameters rdn_generate refuses raise ValueError before anything touches the device."""
+    n, seed, first_index, L, snr_lo, snr_hi, extreme_noise_prob, max_repeat = check_generate_args(
+        n, seed, first_index, signal_length, snr_range, extreme_noise_prob, max_repeat)
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("raman_mi355x runs on the GPU only: the simulator needs a CUDA device")
-    L = int(signal_length)
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
     if out is None:
@@ -385,8 +419,8 @@ def generate(n, seed, first_index=0, signal_length=10000, snr_range=(20.0, 37.0)
             raise ValueError("clean and noisy output buffers must be distinct")
     snr = torch.empty(n, dtype=torch.float32, device=device)
     nstd = torch.empty(n, dtype=torch.float32, device=device)
-    prm = _lib.GenParams(L, float(snr_range[0]), float(snr_range[1]), float(extreme_noise_prob), int(max_repeat))
-    _lib.check(_lib.lib().rdn_generate(int(seed), int(first_index), int(n), ctypes.byref(prm),
+    prm = _lib.GenParams(L, snr_lo, snr_hi, extreme_noise_prob, max_repeat)
+    _lib.check(_lib.lib().rdn_generate(seed, first_index, n, ctypes.byref(prm),
                                        ctypes.c_void_p(clean.data_ptr()), ctypes.c_void_p(noisy.data_ptr()),
                                        ctypes.c_void_p(snr.data_ptr()), ctypes.c_void_p(nstd.data_ptr()),
                                        _stream(device)), "rdn_generate")

@@ -213,7 +213,15 @@ typedef struct {
 
 /* Generate spectra first_index .. first_index+n-1 of the stream `seed` (counter-based Philox,
  * so any index range is reproducible on any device).  clean/noisy: fp32 [n][L] device;
- * snr_db / noise_std: fp32 [n] device (either may be NULL). */
+ * snr_db / noise_std: fp32 [n] device (either may be NULL).
+ * Parameters (RDN_EINVAL otherwise, checked before any device call, also for n = 0):
+ *   1 <= signal_length <= INT32_MAX and max_repeat >= 1 with
+ *   signal_length + 256 * max_repeat <= INT32_MAX (the kernel sums 256 segment lengths per pass in
+ *   32 bits; at signal_length = 1000 the largest max_repeat is 8388604);
+ *   snr_lo and snr_hi finite with snr_lo <= snr_hi; extreme_noise_prob not NaN (values <= 0 never
+ *   spike, values >= 1 always do).
+ * The spectrum index is first_index + i in 64 bits: a caller keeps first_index + n <= 2^64, past
+ * which the index would wrap onto spectrum 0. */
 int rdn_generate(uint64_t seed, uint64_t first_index, int64_t n, const rdn_gen_params* params,
                  float* clean, float* noisy, float* snr_db, float* noise_std, void* stream);
 

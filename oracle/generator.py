@@ -15,6 +15,11 @@ Philox4x32-10 stream on (seed, spectrum index, draw tag, draw index) so that any
 generated independently on any GPU; this module reproduces those draws exactly (integer draws
 bit-exact, float transforms in the same float32 op order).  Parity with the reference itself is
 statistical (tests/test_generator_gpu.py, against tests/golden/generator_stats.json).
+
+``philox4x32`` is pinned to Random123's known-answer vectors, and the noise drawn here to sampling
+theory, in tests/test_generator_cpu.py.  ``seed`` and the spectrum index are unsigned 64-bit: the key
+is (seed & 2^32-1, seed >> 32), the counter words 2 and 3 are (index & 2^32-1, index >> 32), and
+nothing wraps -- callers keep first_index + n <= 2^64 (engine.generate refuses anything else).
 """
 import numpy as np
 

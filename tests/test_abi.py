@@ -197,6 +197,43 @@ def test_errors_are_reported_not_raised(lib):
     assert b"overlap" in lib.rdn_last_error()
 
 
+def _generate_rc(lib, **kw):
+    """rdn_generate with n = 0 and null buffers: the parameter checks run, nothing touches the device."""
+    from raman_mi355x import _lib
+    p = dict(signal_length=1000, snr_lo=20.0, snr_hi=37.0, extreme_noise_prob=0.05, max_repeat=40)
+    p.update(kw)
+    prm = _lib.GenParams(p["signal_length"], p["snr_lo"], p["snr_hi"], p["extreme_noise_prob"], p["max_repeat"])
+    return lib.rdn_generate(1, 0, 0, ctypes.byref(prm), None, None, None, None, None)
+
+
+# signal_length + 256 * max_repeat <= INT32_MAX (include/raman_mi355x.h): at L = 1000 the kernel's 32-bit
+# scan of 256 segment lengths holds up to max_repeat = (2^31 - 1 - 1000) // 256
+MAX_REPEAT_L1000 = (2 ** 31 - 1 - 1000) // 256
+INF, NAN = float("inf"), float("nan")
+
+
+@pytest.mark.parametrize("kw", [
+    dict(max_repeat=2 ** 31 - 1), dict(max_repeat=MAX_REPEAT_L1000 + 1), dict(max_repeat=0),
+    dict(snr_lo=NAN), dict(snr_hi=NAN), dict(snr_lo=-INF), dict(snr_hi=INF), dict(snr_lo=INF, snr_hi=INF),
+    dict(snr_lo=37.0, snr_hi=20.0), dict(extreme_noise_prob=NAN), dict(signal_length=0), dict(signal_length=2 ** 31),
+    dict(signal_length=2 ** 31 - 1, max_repeat=1),
+], ids=lambda d: ",".join(f"{k}={v}" for k, v in d.items()))
+def test_generate_refuses_parameters_its_kernel_cannot_take(lib, kw):
+    """RDN_EINVAL, reported not raised, before any device call: a max_repeat whose 256-length scan can
+    pass INT32_MAX (or whose + 1 overflows), non-finite SNR bounds, a NaN spike probability."""
+    assert MAX_REPEAT_L1000 == 8388604
+    assert _generate_rc(lib, **kw) == -1
+    assert b"rdn_generate" in lib.rdn_last_error()
+
+
+@pytest.mark.parametrize("kw", [
+    dict(), dict(max_repeat=MAX_REPEAT_L1000), dict(max_repeat=1), dict(snr_lo=5.0, snr_hi=5.0),
+    dict(extreme_noise_prob=0.0), dict(extreme_noise_prob=1.0), dict(signal_length=2 ** 31 - 1 - 256, max_repeat=1),
+], ids=lambda d: ",".join(f"{k}={v}" for k, v in d.items()) or "defaults")
+def test_generate_admits_the_edges_of_its_domain(lib, kw):
+    assert _generate_rc(lib, **kw) == 0
+
+
 def _fold(sd, conv, bn):
     w = sd[conv + ".weight"].double().numpy()
     b = sd[conv + ".bias"].double().numpy()
