@@ -13,6 +13,13 @@
 // integer accumulator (RDN_ACC_LIMBS int64 limbs of 32 bits per metric, weight 2^(32 j - 128)), so the
 // sums are the same bits whatever the order of the atomics, the batch split or the number of ranks
 // whose accumulators are all-reduced; rdn_acc_value rounds once.
+//
+// Non-finite values (the contract beside rdn_metrics in include/raman_mi355x.h): every metric is the
+// IEEE / numpy value of its definition.  The sums propagate NaN and inf through the arithmetic; the
+// extrema (Peak2Peak, SSIM's data range) are made NaN for a NaN among their values by tests of the loaded
+// values' bits (nan_bits), since max / min drop a NaN operand and this header is also compiled with
+// -fno-honor-nans inside the walk kernels.  A non-finite metric is stored as it is and raises its
+// out-of-range word in `acc` (to_limbs).
 #pragma once
 #include "common.hpp"
 
@@ -32,26 +39,47 @@ __device__ __forceinline__ T block_reduce(T v, T* scratch, Op op) {
   for (int i = 1; i < MET_THREADS / 64; ++i) r = op(r, scratch[i]);
   return r;
 }
+// NaN by the bits of a loaded value, never by a floating-point comparison: the walk kernels' translation
+// units are built with -fno-honor-nans, under which the compiler may fold `x != x` away, and fmax /
+// fmin / `a > b ? a : b` drop a NaN operand in either build.  Integer tests of the bits mean the same in both.
+__device__ __forceinline__ bool nan_bits(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
+__device__ __forceinline__ bool nan_bits(double v) {
+  return ((unsigned long long)__double_as_longlong(v) & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
+}
+constexpr long long QNAN_BITS = 0x7ff8000000000000ll;
+
 // Six reductions in one round trip through the scratch (each value reduced exactly as block_reduce
-// would: lane butterfly, then the waves in order): sums [0, 2), maxima [2, 4), minima [4, 6)
+// would: lane butterfly, then the waves in order): sums [0, 2), maxima [2, 4), minima [4, 6).
+// The extrema are of y (2, 4) and of clean (3, 5); nan_y / nan_c: this thread loaded a NaN y / clean
+// value.  A wave that holds one publishes NaN for that row's two extrema, and a published NaN makes the
+// result NaN (numpy's max / min), all by bits; rows without a NaN reduce exactly as before.
 constexpr int RED_DOUBLES = 6 * (MET_THREADS / 64);
-__device__ __forceinline__ void block_reduce6(double (&v)[6], double* scratch) {
+__device__ __forceinline__ void block_reduce6(double (&v)[6], bool nan_y, bool nan_c, double* scratch) {
   const int w = __builtin_amdgcn_workitem_id_x() >> 6, lane = __builtin_amdgcn_workitem_id_x() & 63;
   auto op = [](int k, double a, double b) { return k < 2 ? a + b : k < 4 ? (a > b ? a : b) : (a < b ? a : b); };
 #pragma unroll
   for (int k = 0; k < 6; ++k)
     for (int o = 32; o > 0; o >>= 1) v[k] = op(k, v[k], __shfl_xor(v[k], o));
+  const bool wave_nan[2] = {__ballot(nan_y) != 0, __ballot(nan_c) != 0};
+  long long* sb = (long long*)scratch;
   __syncthreads();
   if (lane == 0) {
 #pragma unroll
-    for (int k = 0; k < 6; ++k) scratch[k * (MET_THREADS / 64) + w] = v[k];
+    for (int k = 0; k < 6; ++k)
+      sb[k * (MET_THREADS / 64) + w] = k >= 2 && wave_nan[k & 1] ? QNAN_BITS : __double_as_longlong(v[k]);
   }
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
-    double r = scratch[k * (MET_THREADS / 64)];
-    for (int i = 1; i < MET_THREADS / 64; ++i) r = op(k, r, scratch[k * (MET_THREADS / 64) + i]);
-    v[k] = r;
+    long long b = sb[k * (MET_THREADS / 64)];
+    double r = __longlong_as_double(b);
+    bool nan = k >= 2 && nan_bits(r);
+    for (int i = 1; i < MET_THREADS / 64; ++i) {
+      b = sb[k * (MET_THREADS / 64) + i];
+      nan |= k >= 2 && nan_bits(__longlong_as_double(b));
+      r = op(k, r, __longlong_as_double(b));
+    }
+    v[k] = __longlong_as_double(nan ? QNAN_BITS : __double_as_longlong(r));
   }
 }
 
@@ -89,8 +117,13 @@ __device__ __forceinline__ void spectrum_metrics(YV yv, const TC* __restrict__ c
   const auto add = [](double a, double b) { return a + b; };
 
   double se = 0.0, sm = 0.0, ymax = -INFINITY, ymin = INFINITY, cmax = -INFINITY, cmin = INFINITY;
+  bool nan_y = false, nan_c = false;
   for (int p = tid; p < L; p += MET_THREADS) {
-    const double a = yv(p), c = cc[p];
+    const float af = yv(p);
+    const TC cv = cc[p];
+    nan_y |= nan_bits(af);
+    nan_c |= nan_bits(cv);
+    const double a = af, c = cv;
     se += (a - c) * (a - c);
     if (p + 1 < L) sm += fabs((double)yv(p + 1) - a);
     ymax = fmax(ymax, a);
@@ -99,10 +132,14 @@ __device__ __forceinline__ void spectrum_metrics(YV yv, const TC* __restrict__ c
     cmin = fmin(cmin, c);
   }
   double r6[6] = {se, sm, ymax, cmax, ymin, cmin};
-  block_reduce6(r6, red);
+  block_reduce6(r6, nan_y, nan_c, red);
   se = r6[0], sm = r6[1], ymax = r6[2], cmax = r6[3], ymin = r6[4], cmin = r6[5];
 
-  const double R = cmax - cmin;
+  // max - min, NaN if either is (a NaN among the contributing values), again selected by bits
+  const auto range = [](double hi, double lo) {
+    return __longlong_as_double(nan_bits(hi) || nan_bits(lo) ? QNAN_BITS : __double_as_longlong(hi - lo));
+  };
+  const double R = range(cmax, cmin);
   const double C1 = (0.01 * R) * (0.01 * R), C2 = (0.03 * R) * (0.03 * R);
   const double cov = 7.0 / 6.0;
   double ss = 0.0;
@@ -125,7 +162,7 @@ __device__ __forceinline__ void spectrum_metrics(YV yv, const TC* __restrict__ c
   }
   ss = block_reduce(ss, red, add);
 
-  const double m4[4] = {se / L, ss / (L - 6), sm / (L - 1), ymax - ymin};
+  const double m4[4] = {se / L, ss / (L - 6), sm / (L - 1), range(ymax, ymin)};
   if (tid == 0) {
     if (mo.per) {
       for (int k = 0; k < 4; ++k) mo.per[n * 4 + k] = m4[k];

@@ -228,7 +228,15 @@ int rdn_generate(uint64_t seed, uint64_t first_index, int64_t n, const rdn_gen_p
 /* Per-spectrum MSE, SSIM, Smoothness, Peak2Peak of denoised y against clean (both fp32 [n][L],
  * device), computed in fp64.  per_spectrum: fp64 [n][4] device (may be NULL).  sums: fp64 [5]
  * device, ACCUMULATED (+=) as {ΣMSE, ΣSSIM, ΣSmoothness, ΣPeak2Peak, count} (may be NULL).
- * L must be >= 7 (SSIM window). */
+ * L must be >= 7 (SSIM window).
+ * Non-finite values: every metric is the IEEE / numpy value of its definition.  Peak2Peak (np.max(y) -
+ * np.min(y)) and SSIM's data range (max - min of clean) are NaN if any contributing value is NaN, and
+ * +-inf or NaN as max - min gives otherwise; MSE, Smoothness and SSIM are the IEEE sums (NaN for a NaN
+ * or an inf - inf among the terms, else +inf for an infinite term; a 0/0 SSIM window -- all-zero rows --
+ * gives NaN).  A non-finite metric is written as it is to per_spectrum and sums and counted in the
+ * out-of-range word of that metric in acc: never clamped, never skipped.  The metric epilogue of
+ * rdn_forward_metrics follows the same contract (a saturated spectrum's NaN outputs give four NaN metrics).
+ * fp32 subnormals in y and clean are read as their values, not flushed to zero. */
 int rdn_metrics(const float* y, const float* clean, int64_t n, int64_t L, double* per_spectrum,
                 double* sums, void* stream);
 
