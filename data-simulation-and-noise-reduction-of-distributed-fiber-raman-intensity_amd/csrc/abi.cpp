@@ -459,14 +459,38 @@ static double acc_to_double(const int64_t* limb) {
   return neg ? -v : v;
 }
 
+// Rows of accumulators -> doubles (rdn_acc_value, rdn_report_value, rdn_physics_value).  A row of
+// row_words words is `quantities` accumulators of RDN_ACC_STRIDE words and then `counts` count words; it
+// becomes quantities + counts doubles: the first `lead` counts, the quantities (NaN where the out-of-range
+// word is set), the other counts.  With `totals` one more row follows: the integer sums of the rows'
+// words (at most 66 rows of |limb| < 2^63 / 66: a report holds up to 2^31 spectra of 32-bit chunks),
+// added without sign overflow in unsigned arithmetic.
+static void acc_rows_value(const int64_t* words, int rows, int row_words, int quantities, int counts, int lead,
+                           bool totals, double* out) {
+  const int values = quantities + counts;
+  int64_t total[RDN_REPORT_ROW_WORDS] = {};
+  auto row_value = [&](const int64_t* r, double* o) {
+    const int64_t* c = r + quantities * RDN_ACC_STRIDE;
+    for (int i = 0; i < lead; ++i) o[i] = (double)c[i];
+    for (int k = 0; k < quantities; ++k) {
+      const int64_t* a = r + k * RDN_ACC_STRIDE;
+      o[lead + k] = a[RDN_ACC_LIMBS] ? std::nan("") : acc_to_double(a);
+    }
+    for (int i = lead; i < counts; ++i) o[quantities + i] = (double)c[i];
+  };
+  for (int b = 0; b < rows; ++b) {
+    const int64_t* r = words + (size_t)b * row_words;
+    row_value(r, out + (size_t)b * values);
+    for (int w = 0; w < row_words; ++w) total[w] = (int64_t)((uint64_t)total[w] + (uint64_t)r[w]);
+  }
+  if (totals) row_value(total, out + (size_t)rows * values);
+}
+static_assert(RDN_ACC_WORDS <= RDN_REPORT_ROW_WORDS && RDN_PHYS_ROW_WORDS <= RDN_REPORT_ROW_WORDS, "total[]");
+
 int rdn_acc_value(const int64_t* acc, double* sums) {
   RDN_GUARD_BEGIN
   if (!acc || !sums) return fail(RDN_EINVAL, "rdn_acc_value: null pointer");
-  for (int k = 0; k < 4; ++k) {
-    const int64_t* a = acc + k * RDN_ACC_STRIDE;
-    sums[k] = a[RDN_ACC_LIMBS] ? std::nan("") : acc_to_double(a);
-  }
-  sums[4] = (double)acc[RDN_ACC_COUNT];
+  acc_rows_value(acc, 1, RDN_ACC_WORDS, 4, 1, 0, false, sums);
   return RDN_OK;
   RDN_GUARD_END
 }
@@ -477,19 +501,37 @@ static bool valid_bins(float lo, float hi, int nbins) {
 }
 static const char* bins_msg() { return "need 1 <= nbins <= 64 and finite lo < hi"; }
 
+// The arguments rdn_snr and rdn_physics share, checked in the order their errors have always been
+// reported in.  rows: x, y and clean are all given; weights_ok: rdn_physics's weights are finite;
+// fed: NULL, or the inputs given that only a report reads ("key feeds"); per_name: the per-spectrum output.
+static int check_report_call(const std::string& fn, int64_t min_L, bool rows, int clean_is_f64, int64_t n, int64_t L,
+                             bool weights_ok, const void* report, float lo, float hi, int nbins, const char* fed,
+                             const void* per, const char* per_name) {
+  if (n > 0 && !rows) return fail(RDN_EINVAL, fn + ": null pointer");
+  if (clean_is_f64 != 0 && clean_is_f64 != 1) return fail(RDN_EINVAL, fn + ": clean_is_f64 must be 0 or 1");
+  if (n < 0 || L < min_L || L > 0x7fffffff)
+    return fail(RDN_EINVAL, fn + ": need n >= 0 and " + std::to_string(min_L) + " <= L < 2^31");
+  if (!weights_ok) return fail(RDN_EINVAL, fn + ": the weights alpha, beta, gamma must be finite");
+  if (report && !valid_bins(lo, hi, nbins)) return fail(RDN_EINVAL, fn + ": " + bins_msg());
+  if (!report && fed) return fail(RDN_EINVAL, fn + ": " + fed + " the report, which is NULL");
+  if (!report && !per) return fail(RDN_EINVAL, fn + ": neither " + per_name + " nor report to write");
+  return RDN_OK;
+}
+static int check_report_value(const std::string& fn, const int64_t* report, int nbins, const double* out) {
+  if (!report || !out) return fail(RDN_EINVAL, fn + ": null pointer");
+  if (nbins < 1 || nbins > RDN_REPORT_MAX_BINS) return fail(RDN_EINVAL, fn + ": need 1 <= nbins <= 64");
+  return RDN_OK;
+}
+
 int rdn_snr(const float* x, const float* y, const void* clean, int clean_is_f64, int64_t n, int64_t L,
             double* per_spectrum3, const float* key, float lo, float hi, int nbins, const double* per4,
             int64_t* report, void* stream) {
   RDN_GUARD_BEGIN
-  if (n > 0 && (!x || !y || !clean)) return fail(RDN_EINVAL, "rdn_snr: null pointer");
-  if (clean_is_f64 != 0 && clean_is_f64 != 1) return fail(RDN_EINVAL, "rdn_snr: clean_is_f64 must be 0 or 1");
-  if (n < 0 || L < 1 || L > 0x7fffffff) return fail(RDN_EINVAL, "rdn_snr: need n >= 0 and 1 <= L < 2^31");
-  if (report && !valid_bins(lo, hi, nbins)) return fail(RDN_EINVAL, std::string("rdn_snr: ") + bins_msg());
-  if (!report && (key || per4)) return fail(RDN_EINVAL, "rdn_snr: key / per4 feed the report, which is NULL");
-  if (!report && !per_spectrum3) return fail(RDN_EINVAL, "rdn_snr: neither per_spectrum3 nor report to write");
-  if (n == 0) return RDN_OK;
+  const int rc = check_report_call("rdn_snr", 1, x && y && clean, clean_is_f64, n, L, true, report, lo, hi, nbins,
+                                   key || per4 ? "key / per4 feed" : nullptr, per_spectrum3, "per_spectrum3");
+  if (rc != RDN_OK || n == 0) return rc;
   const rdn::snr::SnrOut so{per_spectrum3, key, per4, (long long*)report,
-                            report ? rdn::snr::make_bins(lo, hi, nbins) : rdn::snr::Bins{0.f, 0.f, 0.f, 0}};
+                            report ? rdn::make_bins(lo, hi, nbins) : rdn::Bins{0.f, 0.f, 0.f, 0}};
   return hip_check(rdn::launch_snr(x, y, clean, clean_is_f64 == 1, n, (int)L, so, (hipStream_t)stream), "snr");
   RDN_GUARD_END
 }
@@ -498,33 +540,16 @@ int rdn_report_bin(float key, float lo, float hi, int nbins, int* row) {
   RDN_GUARD_BEGIN
   if (!row) return fail(RDN_EINVAL, "rdn_report_bin: null pointer");
   if (!valid_bins(lo, hi, nbins)) return fail(RDN_EINVAL, std::string("rdn_report_bin: ") + bins_msg());
-  *row = rdn::snr::bin_row(key, rdn::snr::make_bins(lo, hi, nbins));
+  *row = rdn::bin_row(key, rdn::make_bins(lo, hi, nbins));
   return RDN_OK;
   RDN_GUARD_END
 }
 
 int rdn_report_value(const int64_t* report, int nbins, double* out) {
   RDN_GUARD_BEGIN
-  if (!report || !out) return fail(RDN_EINVAL, "rdn_report_value: null pointer");
-  if (nbins < 1 || nbins > RDN_REPORT_MAX_BINS) return fail(RDN_EINVAL, "rdn_report_value: need 1 <= nbins <= 64");
-  const int rows = RDN_REPORT_ROWS(nbins);
-  // the totals row: integer sums of the rows' words (at most 66 rows of |limb| < 2^63 / 66: a report
-  // holds up to 2^31 spectra of 32-bit chunks), added without sign overflow in unsigned arithmetic
-  int64_t total[RDN_REPORT_ROW_WORDS] = {};
-  auto values = [](const int64_t* r, double* o) {
-    o[0] = (double)r[RDN_REPORT_COUNT];
-    for (int k = 0; k < RDN_REPORT_QUANTITIES; ++k) {
-      const int64_t* a = r + k * RDN_ACC_STRIDE;
-      o[1 + k] = a[RDN_ACC_LIMBS] ? std::nan("") : acc_to_double(a);
-    }
-    o[1 + RDN_REPORT_QUANTITIES] = (double)r[RDN_REPORT_COUNT4];
-  };
-  for (int b = 0; b < rows; ++b) {
-    const int64_t* r = report + (size_t)b * RDN_REPORT_ROW_WORDS;
-    values(r, out + (size_t)b * RDN_REPORT_VALUES);
-    for (int w = 0; w < RDN_REPORT_ROW_WORDS; ++w) total[w] = (int64_t)((uint64_t)total[w] + (uint64_t)r[w]);
-  }
-  values(total, out + (size_t)rows * RDN_REPORT_VALUES);
+  const int rc = check_report_value("rdn_report_value", report, nbins, out);
+  if (rc != RDN_OK) return rc;
+  acc_rows_value(report, RDN_REPORT_ROWS(nbins), RDN_REPORT_ROW_WORDS, RDN_REPORT_QUANTITIES, 2, 1, true, out);
   return RDN_OK;
   RDN_GUARD_END
 }
@@ -533,17 +558,12 @@ int rdn_physics(const float* x, const float* y, const void* clean, int clean_is_
                 double alpha, double beta, double gamma, double* per_spectrum6, const float* key, float lo,
                 float hi, int nbins, int64_t* report, void* stream) {
   RDN_GUARD_BEGIN
-  if (n > 0 && (!x || !y || !clean)) return fail(RDN_EINVAL, "rdn_physics: null pointer");
-  if (clean_is_f64 != 0 && clean_is_f64 != 1) return fail(RDN_EINVAL, "rdn_physics: clean_is_f64 must be 0 or 1");
-  if (n < 0 || L < 3 || L > 0x7fffffff) return fail(RDN_EINVAL, "rdn_physics: need n >= 0 and 3 <= L < 2^31");
-  if (!std::isfinite(alpha) || !std::isfinite(beta) || !std::isfinite(gamma))
-    return fail(RDN_EINVAL, "rdn_physics: the weights alpha, beta, gamma must be finite");
-  if (report && !valid_bins(lo, hi, nbins)) return fail(RDN_EINVAL, std::string("rdn_physics: ") + bins_msg());
-  if (!report && key) return fail(RDN_EINVAL, "rdn_physics: key feeds the report, which is NULL");
-  if (!report && !per_spectrum6) return fail(RDN_EINVAL, "rdn_physics: neither per_spectrum6 nor report to write");
-  if (n == 0) return RDN_OK;
+  const int rc = check_report_call("rdn_physics", 3, x && y && clean, clean_is_f64, n, L,
+                                   std::isfinite(alpha) && std::isfinite(beta) && std::isfinite(gamma), report, lo, hi,
+                                   nbins, key ? "key feeds" : nullptr, per_spectrum6, "per_spectrum6");
+  if (rc != RDN_OK || n == 0) return rc;
   const rdn::phys::PhysOut po{per_spectrum6, key, (long long*)report,
-                              report ? rdn::snr::make_bins(lo, hi, nbins) : rdn::snr::Bins{0.f, 0.f, 0.f, 0},
+                              report ? rdn::make_bins(lo, hi, nbins) : rdn::Bins{0.f, 0.f, 0.f, 0},
                               alpha, beta, gamma};
   return hip_check(rdn::launch_physics(x, y, clean, clean_is_f64 == 1, n, (int)L, po, (hipStream_t)stream), "physics");
   RDN_GUARD_END
@@ -551,24 +571,9 @@ int rdn_physics(const float* x, const float* y, const void* clean, int clean_is_
 
 int rdn_physics_value(const int64_t* report, int nbins, double* out) {
   RDN_GUARD_BEGIN
-  if (!report || !out) return fail(RDN_EINVAL, "rdn_physics_value: null pointer");
-  if (nbins < 1 || nbins > RDN_REPORT_MAX_BINS) return fail(RDN_EINVAL, "rdn_physics_value: need 1 <= nbins <= 64");
-  const int rows = RDN_REPORT_ROWS(nbins);
-  // the totals row: integer sums of the rows' words, added in unsigned arithmetic (rdn_report_value)
-  int64_t total[RDN_PHYS_ROW_WORDS] = {};
-  auto values = [](const int64_t* r, double* o) {
-    o[0] = (double)r[RDN_PHYS_COUNT];
-    for (int k = 0; k < RDN_PHYS_QUANTITIES; ++k) {
-      const int64_t* a = r + k * RDN_ACC_STRIDE;
-      o[1 + k] = a[RDN_ACC_LIMBS] ? std::nan("") : acc_to_double(a);
-    }
-  };
-  for (int b = 0; b < rows; ++b) {
-    const int64_t* r = report + (size_t)b * RDN_PHYS_ROW_WORDS;
-    values(r, out + (size_t)b * RDN_PHYS_VALUES);
-    for (int w = 0; w < RDN_PHYS_ROW_WORDS; ++w) total[w] = (int64_t)((uint64_t)total[w] + (uint64_t)r[w]);
-  }
-  values(total, out + (size_t)rows * RDN_PHYS_VALUES);
+  const int rc = check_report_value("rdn_physics_value", report, nbins, out);
+  if (rc != RDN_OK) return rc;
+  acc_rows_value(report, RDN_REPORT_ROWS(nbins), RDN_PHYS_ROW_WORDS, RDN_PHYS_QUANTITIES, 1, 1, true, out);
   return RDN_OK;
   RDN_GUARD_END
 }

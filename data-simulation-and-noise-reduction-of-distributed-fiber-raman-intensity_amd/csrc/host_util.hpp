@@ -81,6 +81,21 @@ inline hipError_t read_words(void* out, const void* dev_words, size_t bytes, hip
   return e;
 }
 
+// The meters' clean reference is fp32 or fp64: f(clean as a pointer of its own type).
+template <class F>
+inline hipError_t with_clean(const void* clean, bool clean_f64, F f) {
+  return clean_f64 ? f((const double*)clean) : f((const float*)clean);
+}
+
+// Walks a batch of n workgroups (one per spectrum) in launches of at most 2^31 - 1, the grid's limit in
+// x: launch(n0, nn) enqueues the nn of them that start at n0.
+template <class Launch>
+inline hipError_t launch_chunks(int64_t n, Launch launch) {
+  const int64_t chunk = 0x7fffffff;
+  for (int64_t n0 = 0; n0 < n; n0 += chunk) launch(n0, n - n0 < chunk ? n - n0 : chunk);
+  return hipGetLastError();
+}
+
 // Compute units of device `dev` (0 if the query fails), cached per device.
 inline int device_cus(int dev) {
   static std::atomic<int> cus[MAX_DEVICES];

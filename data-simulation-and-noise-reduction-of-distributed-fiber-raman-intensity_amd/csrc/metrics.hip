@@ -9,6 +9,7 @@
 // The clean reference is read as fp32 (the on-device simulator's output) or fp64 (a test.npz loaded
 // as the reference loads it, 数据集产生.py:73-78 / evaulate.py:61-62: the metrics then see the same
 // float64 clean values as evaulate.py:34-35).
+#include "host_util.hpp"
 #include "metrics.hpp"
 
 namespace rdn {
@@ -25,23 +26,15 @@ __global__ __launch_bounds__(MET_THREADS) void metrics_kernel(const float* __res
 
 }  // namespace met
 
-template <typename TC>
-static hipError_t launch_metrics_t(const float* y, const TC* clean, int64_t n, int L, double* per, double* sums,
-                                   long long* acc, hipStream_t stream) {
-  const int64_t chunk = 0x7fffffff;
-  for (int64_t n0 = 0; n0 < n; n0 += chunk) {
-    const int64_t nn = n - n0 < chunk ? n - n0 : chunk;
-    const met::MetricOut mo{clean + n0 * L, sizeof(TC) == 8, per ? per + n0 * 4 : nullptr, sums, acc};
-    hipLaunchKernelGGL(met::metrics_kernel<TC>, dim3((unsigned)nn), dim3(met::MET_THREADS), 0, stream, y + n0 * L,
-                       clean + n0 * L, L, mo);
-  }
-  return hipGetLastError();
-}
-
 hipError_t launch_metrics(const float* y, const void* clean, bool clean_f64, int64_t n, int L, double* per,
                           double* sums, long long* acc, hipStream_t stream) {
-  return clean_f64 ? launch_metrics_t(y, (const double*)clean, n, L, per, sums, acc, stream)
-                   : launch_metrics_t(y, (const float*)clean, n, L, per, sums, acc, stream);
+  return with_clean(clean, clean_f64, [&](auto* cc) {
+    return launch_chunks(n, [&](int64_t n0, int64_t nn) {
+      const met::MetricOut mo{cc + n0 * L, sizeof(*cc) == 8, per ? per + n0 * 4 : nullptr, sums, acc};
+      hipLaunchKernelGGL(met::metrics_kernel, dim3((unsigned)nn), dim3(met::MET_THREADS), 0, stream, y + n0 * L,
+                         cc + n0 * L, L, mo);
+    });
+  });
 }
 
 }  // namespace rdn

@@ -107,6 +107,22 @@ __device__ __forceinline__ bool to_limbs(double v, long long (&limb)[RDN_ACC_LIM
   return true;
 }
 
+// Adds v, without rounding, to quantity q's accumulator (RDN_ACC_STRIDE words from acc + q * RDN_ACC_STRIDE):
+// the non-zero limbs by integer atomics (order-free), or one count into the quantity's out-of-range word
+// if v has no limbs.
+__device__ __forceinline__ void acc_add(long long* acc, int q, double v) {
+  long long limb[RDN_ACC_LIMBS];
+  const bool ok = to_limbs(v, limb);
+  long long* a = acc + q * RDN_ACC_STRIDE;
+  if (ok) {
+#pragma unroll
+    for (int j = 0; j < RDN_ACC_LIMBS; ++j)
+      if (limb[j]) atomicAdd((unsigned long long*)&a[j], (unsigned long long)limb[j]);
+  } else {
+    atomicAdd((unsigned long long*)&a[RDN_ACC_LIMBS], 1ull);
+  }
+}
+
 // The four metrics of spectrum n (denoised values through yv(p), clean cc[0..L)), every thread of the
 // MET_THREADS-thread workgroup taking part; red: RED_DOUBLES doubles of LDS.  Results: per[n],
 // sums, acc of mo (each optional).
@@ -174,16 +190,7 @@ __device__ __forceinline__ void spectrum_metrics(YV yv, const TC* __restrict__ c
   }
   // exact accumulator: lanes 0..3 of wave 0 each own one metric (integer atomics: order-free)
   if (mo.acc && tid < 4) {
-    long long limb[RDN_ACC_LIMBS];
-    const bool ok = to_limbs(m4[tid], limb);
-    long long* a = mo.acc + tid * RDN_ACC_STRIDE;
-    if (ok) {
-#pragma unroll
-      for (int j = 0; j < RDN_ACC_LIMBS; ++j)
-        if (limb[j]) atomicAdd((unsigned long long*)&a[j], (unsigned long long)limb[j]);
-    } else {
-      atomicAdd((unsigned long long*)&a[RDN_ACC_LIMBS], 1ull);   // this metric's out-of-range count
-    }
+    acc_add(mo.acc, tid, m4[tid]);
     if (tid == 0) atomicAdd((unsigned long long*)&mo.acc[RDN_ACC_COUNT], 1ull);
   }
 }

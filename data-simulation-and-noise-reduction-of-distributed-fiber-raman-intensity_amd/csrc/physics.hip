@@ -2,8 +2,8 @@
 // of the loss PIDN and APIDN are trained against, their weighted total and the number of masked
 // positions, from the noisy input x, the denoised y and clean (definitions, report layout:
 // include/raman_mi355x.h rdn_physics; physics.hpp).  The reduction and the exact integer accumulators are
-// the metrics kernel's (metrics.hpp block_reduce / to_limbs), the bin formula is the SNR report's
-// (snr.hpp bin_row): a report's words are the same bits whatever the batch split, the atomics' order or
+// the metrics kernel's (metrics.hpp block_reduce / acc_add), the bin formula is every binned report's
+// (report.hpp bin_row): a report's words are the same bits whatever the batch split, the atomics' order or
 // the number of ranks whose reports are summed.
 //
 // Reference: PIDN/train.py:109-146 (F.mse_loss, F.l1_loss of the first differences, the
@@ -19,6 +19,7 @@
 // and the terms that do not exist are selected away, so that no load sits behind a branch.
 //
 // Rows are addressed as pointer + 64-bit offset (no buffer descriptor), so any L < 2^31 runs.
+#include "host_util.hpp"
 #include "metrics.hpp"
 #include "physics.hpp"
 
@@ -93,47 +94,30 @@ __global__ __launch_bounds__(MET_THREADS) void physics_kernel(const float* __res
   }
   if (!po.report) return;
 
-  long long* row = po.report + (size_t)(po.key ? snr::bin_row(po.key[n], po.bins) : 1) * RDN_PHYS_ROW_WORDS;
+  long long* row = po.report + (size_t)(po.key ? bin_row(po.key[n], po.bins) : 1) * RDN_PHYS_ROW_WORDS;
   // lanes 0..5 of wave 0 each own one quantity (integer atomics: order-free)
   if (tid < RDN_PHYS_QUANTITIES) {
     double v = v6[0];
 #pragma unroll
     for (int k = 1; k < RDN_PHYS_QUANTITIES; ++k) v = tid == k ? v6[k] : v;
-    long long limb[RDN_ACC_LIMBS];
-    const bool ok = met::to_limbs(v, limb);
-    long long* a = row + tid * RDN_ACC_STRIDE;
-    if (ok) {
-#pragma unroll
-      for (int j = 0; j < RDN_ACC_LIMBS; ++j)
-        if (limb[j]) atomicAdd((unsigned long long*)&a[j], (unsigned long long)limb[j]);
-    } else {
-      atomicAdd((unsigned long long*)&a[RDN_ACC_LIMBS], 1ull);   // this quantity's out-of-range count
-    }
+    met::acc_add(row, tid, v);
   }
   if (tid == 0) atomicAdd((unsigned long long*)&row[RDN_PHYS_COUNT], 1ull);
 }
 
 }  // namespace phys
 
-template <typename TC>
-static hipError_t launch_physics_t(const float* x, const float* y, const TC* clean, int64_t n, int L,
-                                   const phys::PhysOut& po, hipStream_t stream) {
-  const int64_t chunk = 0x7fffffff;
-  for (int64_t n0 = 0; n0 < n; n0 += chunk) {
-    const int64_t nn = n - n0 < chunk ? n - n0 : chunk;
-    phys::PhysOut c = po;
-    c.per6 = po.per6 ? po.per6 + n0 * RDN_PHYS_QUANTITIES : nullptr;
-    c.key = po.key ? po.key + n0 : nullptr;
-    hipLaunchKernelGGL(phys::physics_kernel<TC>, dim3((unsigned)nn), dim3(met::MET_THREADS), 0, stream, x + n0 * L,
-                       y + n0 * L, clean + n0 * L, L, c);
-  }
-  return hipGetLastError();
-}
-
 hipError_t launch_physics(const float* x, const float* y, const void* clean, bool clean_f64, int64_t n, int L,
                           const phys::PhysOut& po, hipStream_t stream) {
-  return clean_f64 ? launch_physics_t(x, y, (const double*)clean, n, L, po, stream)
-                   : launch_physics_t(x, y, (const float*)clean, n, L, po, stream);
+  return with_clean(clean, clean_f64, [&](auto* cc) {
+    return launch_chunks(n, [&](int64_t n0, int64_t nn) {
+      phys::PhysOut c = po;
+      c.per6 = po.per6 ? po.per6 + n0 * RDN_PHYS_QUANTITIES : nullptr;
+      c.key = po.key ? po.key + n0 : nullptr;
+      hipLaunchKernelGGL(phys::physics_kernel, dim3((unsigned)nn), dim3(met::MET_THREADS), 0, stream, x + n0 * L,
+                         y + n0 * L, cc + n0 * L, L, c);
+    });
+  });
 }
 
 }  // namespace rdn

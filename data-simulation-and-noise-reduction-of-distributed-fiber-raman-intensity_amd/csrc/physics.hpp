@@ -5,7 +5,7 @@
 // are trained against, MSE + alpha * smoothness + beta * peak retention + gamma * noise model.
 #pragma once
 #include "common.hpp"
-#include "snr.hpp"
+#include "report.hpp"
 
 namespace rdn {
 namespace phys {
@@ -15,7 +15,7 @@ struct PhysOut {
   double* per6;          // fp64 [n][6] {MSE, Smooth, Peak, Noise, Total, PeakCount}
   const float* key;      // fp32 [n] binning key, NULL: every spectrum into row 1
   long long* report;     // RDN_PHYS_WORDS(bins.nbins) int64, accumulated
-  snr::Bins bins;
+  Bins bins;
   double alpha, beta, gamma;
 };
 

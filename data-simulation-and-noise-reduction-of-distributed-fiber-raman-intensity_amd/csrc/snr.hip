@@ -1,13 +1,14 @@
 // SNR report on the device: one 512-thread workgroup per spectrum makes one pass over the noisy input
 // x, the denoised y and clean, in fp64 (definitions, report layout and bin formula:
-// include/raman_mi355x.h rdn_snr; snr.hpp).  The reduction and the exact integer accumulators are the
-// metrics kernel's (metrics.hpp block_reduce / to_limbs): a report's words are the same bits whatever the
+// include/raman_mi355x.h rdn_snr; report.hpp).  The reduction and the exact integer accumulators are the
+// metrics kernel's (metrics.hpp block_reduce / acc_add): a report's words are the same bits whatever the
 // batch split, the atomics' order or the number of ranks whose reports are summed.
 //
 // Reference: 数据集产生.py:43-45 (P = mean(clean^2) is the power the simulator scales its noise by); the
 // reference's evaulate.py has no SNR, its datasets carry the nominal one (`snrs`, 数据集产生.py:78).
 //
 // Rows are addressed as pointer + 64-bit offset (no buffer descriptor), so any L < 2^31 runs.
+#include "host_util.hpp"
 #include "metrics.hpp"
 #include "snr.hpp"
 
@@ -53,16 +54,7 @@ __global__ __launch_bounds__(MET_THREADS) void snr_kernel(const float* __restric
   // lanes 0..6 of wave 0 each own one quantity (integer atomics: order-free)
   if (tid < RDN_REPORT_QUANTITIES && (tid >= 4 || so.per4)) {
     const double v = tid < 4 ? so.per4[n * 4 + tid] : tid == 4 ? s_in : tid == 5 ? s_out : gain;
-    long long limb[RDN_ACC_LIMBS];
-    const bool ok = met::to_limbs(v, limb);
-    long long* a = row + tid * RDN_ACC_STRIDE;
-    if (ok) {
-#pragma unroll
-      for (int j = 0; j < RDN_ACC_LIMBS; ++j)
-        if (limb[j]) atomicAdd((unsigned long long*)&a[j], (unsigned long long)limb[j]);
-    } else {
-      atomicAdd((unsigned long long*)&a[RDN_ACC_LIMBS], 1ull);   // this quantity's out-of-range count
-    }
+    met::acc_add(row, tid, v);
   }
   if (tid == 0) {
     atomicAdd((unsigned long long*)&row[RDN_REPORT_COUNT], 1ull);
@@ -72,24 +64,16 @@ __global__ __launch_bounds__(MET_THREADS) void snr_kernel(const float* __restric
 
 }  // namespace snr
 
-template <typename TC>
-static hipError_t launch_snr_t(const float* x, const float* y, const TC* clean, int64_t n, int L, const snr::SnrOut& so,
-                               hipStream_t stream) {
-  const int64_t chunk = 0x7fffffff;
-  for (int64_t n0 = 0; n0 < n; n0 += chunk) {
-    const int64_t nn = n - n0 < chunk ? n - n0 : chunk;
-    const snr::SnrOut c{so.per3 ? so.per3 + n0 * 3 : nullptr, so.key ? so.key + n0 : nullptr,
-                        so.per4 ? so.per4 + n0 * 4 : nullptr, so.report, so.bins};
-    hipLaunchKernelGGL(snr::snr_kernel<TC>, dim3((unsigned)nn), dim3(met::MET_THREADS), 0, stream, x + n0 * L,
-                       y + n0 * L, clean + n0 * L, L, c);
-  }
-  return hipGetLastError();
-}
-
 hipError_t launch_snr(const float* x, const float* y, const void* clean, bool clean_f64, int64_t n, int L,
                       const snr::SnrOut& so, hipStream_t stream) {
-  return clean_f64 ? launch_snr_t(x, y, (const double*)clean, n, L, so, stream)
-                   : launch_snr_t(x, y, (const float*)clean, n, L, so, stream);
+  return with_clean(clean, clean_f64, [&](auto* cc) {
+    return launch_chunks(n, [&](int64_t n0, int64_t nn) {
+      const snr::SnrOut c{so.per3 ? so.per3 + n0 * 3 : nullptr, so.key ? so.key + n0 : nullptr,
+                          so.per4 ? so.per4 + n0 * 4 : nullptr, so.report, so.bins};
+      hipLaunchKernelGGL(snr::snr_kernel, dim3((unsigned)nn), dim3(met::MET_THREADS), 0, stream, x + n0 * L,
+                         y + n0 * L, cc + n0 * L, L, c);
+    });
+  });
 }
 
 }  // namespace rdn

@@ -157,6 +157,18 @@ def _check_cuda_f32(t, name):
         raise TypeError(f"{name} must be float32, got {t.dtype}")
 
 
+def _check_clean(clean):
+    """The clean reference of the meters: a CUDA tensor, float32 (the device simulator) or float64."""
+    if not (torch.is_tensor(clean) and clean.is_cuda):
+        raise RuntimeError("raman_mi355x runs on the GPU only: clean must be a CUDA (HIP) tensor")
+    if clean.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"clean must be float32 or float64, got {clean.dtype}")
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+
+
 def _rows(t):
     """(N, L) or (N, 1, L) -> contiguous (N, L) (N = 0 included: no -1 in the shape)."""
     return t.reshape(t.shape[0], t.shape[-1] if t.dim() > 1 else 1).contiguous()
@@ -336,10 +348,7 @@ def forward_metrics(arch, dtype, packed, x, clean, out=None, sums=None, per_spec
     second pass.  Returns (y, per (n, 4) or None, sums, fused)."""
     _check_cuda_f32(x, "input")
     x = x.contiguous()
-    if not (torch.is_tensor(clean) and clean.is_cuda):
-        raise RuntimeError("raman_mi355x runs on the GPU only: clean must be a CUDA (HIP) tensor")
-    if clean.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"clean must be float32 or float64, got {clean.dtype}")
+    _check_clean(clean)
     n, L, a, code, y, ws = _forward_args(arch, dtype, x, out, check, workspace, False)
     clean = _rows(clean)
     if tuple(clean.shape) != (n, L):
@@ -434,10 +443,7 @@ def metrics(y, clean, sums=None, per_spectrum=True, acc=None):
     it; the metrics then see the same float64 clean values as evaulate.py:34-35).  ``acc``: an
     exact accumulator (new_acc) that this batch is added to (rdn_metrics_ex)."""
     _check_cuda_f32(y, "denoised")
-    if not (torch.is_tensor(clean) and clean.is_cuda):
-        raise RuntimeError("raman_mi355x runs on the GPU only: clean must be a CUDA (HIP) tensor")
-    if clean.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"clean must be float32 or float64, got {clean.dtype}")
+    _check_clean(clean)
     y = _rows(y)
     clean = _rows(clean)
     if y.shape != clean.shape:
@@ -478,8 +484,10 @@ def acc_value(acc):
     return out
 
 
-# ---- SNR report (rdn_snr; definitions, bin formula and report layout: include/raman_mi355x.h) ----
+# ---- binned reports (rdn_snr, rdn_physics; definitions, bin formula and report layouts: include/raman_mi355x.h) ----
 REPORT_QUANTITIES = ("MSE", "SSIM", "Smoothness", "Peak2Peak", "SNR_in", "SNR_out", "SNR_gain")
+PHYS_QUANTITIES = ("MSE", "Smooth", "Peak", "Noise", "Total", "PeakCount")
+PHYS_WEIGHTS = (0.1, 0.05, 0.01)          # PIDN/train.py:112 alpha, beta, gamma
 
 
 def _bins(bins):
@@ -496,11 +504,32 @@ def _bins(bins):
     return lo, hi, int(nbins)
 
 
-def new_report(nbins, device):
-    """A zeroed SNR report (RDN_REPORT_WORDS(nbins) int64: nbins + 2 rows) on ``device``."""
+def _weights(weights):
+    """(alpha, beta, gamma) as rdn_physics takes them: three finite floats."""
+    try:
+        a, b, g = (float(w) for w in weights)
+    except (TypeError, ValueError):
+        raise ValueError(f"weights must be (alpha, beta, gamma), got {weights!r}") from None
+    if not all(abs(w) < float("inf") for w in (a, b, g)):          # NaN fails the comparison too
+        raise ValueError(f"weights must be finite, got {(a, b, g)}")
+    return a, b, g
+
+
+def _new_report(nbins, device, words):
+    """A zeroed report of words(nbins) int64 on ``device``."""
     if isinstance(nbins, bool) or int(nbins) != nbins or not 1 <= int(nbins) <= _lib.REPORT_MAX_BINS:
         raise ValueError(f"nbins must be an integer in [1, {_lib.REPORT_MAX_BINS}], got {nbins!r}")
-    return torch.zeros(_lib.report_words(int(nbins)), dtype=torch.int64, device=device)
+    return torch.zeros(words(int(nbins)), dtype=torch.int64, device=device)
+
+
+def new_report(nbins, device):
+    """A zeroed SNR report (RDN_REPORT_WORDS(nbins) int64: nbins + 2 rows) on ``device``."""
+    return _new_report(nbins, device, _lib.report_words)
+
+
+def new_physics_report(nbins, device):
+    """A zeroed PhysicsAwareLoss report (RDN_PHYS_WORDS(nbins) int64: nbins + 2 rows) on ``device``."""
+    return _new_report(nbins, device, _lib.phys_words)
 
 
 def report_bin(key, bins):
@@ -512,22 +541,65 @@ def report_bin(key, bins):
     return row.value
 
 
+def _report_value(report, nbins, what, words, values, fn):
+    """Doubles of a report (float64 (nbins + 3, values), CPU) through the ABI's ``fn``."""
+    nbins = int(nbins)
+    if not 1 <= nbins <= _lib.REPORT_MAX_BINS:
+        raise ValueError(f"nbins must be in [1, {_lib.REPORT_MAX_BINS}], got {nbins}")
+    h = report.detach().to("cpu", torch.int64).contiguous()
+    if h.numel() != words(nbins):
+        raise ValueError(f"a {what} of {nbins} bins has {words(nbins)} words, got {h.numel()}")
+    out = torch.empty((_lib.report_rows(nbins) + 1, values), dtype=torch.float64)
+    _lib.check(getattr(_lib.lib(), fn)(ctypes.cast(h.data_ptr(), ctypes.POINTER(ctypes.c_int64)), nbins,
+                                       ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_double))), fn)
+    return out
+
+
 def report_value(report, nbins):
     """Doubles of a report (float64 (nbins + 3, 9), CPU): one row per report row -- underflow, the bins,
     overflow -- then the totals over all of them; columns {count, ΣMSE, ΣSSIM, ΣSmoothness, ΣPeak2Peak,
     ΣSNR_in, ΣSNR_out, ΣSNR_gain, count of spectra whose four metrics were supplied}.  Each sum is the
     exact total rounded once, NaN where a value was out of range (rdn_report_value)."""
-    nbins = int(nbins)
-    if not 1 <= nbins <= _lib.REPORT_MAX_BINS:
-        raise ValueError(f"nbins must be in [1, {_lib.REPORT_MAX_BINS}], got {nbins}")
-    h = report.detach().to("cpu", torch.int64).contiguous()
-    if h.numel() != _lib.report_words(nbins):
-        raise ValueError(f"a report of {nbins} bins has {_lib.report_words(nbins)} words, got {h.numel()}")
-    out = torch.empty((_lib.report_rows(nbins) + 1, _lib.REPORT_VALUES), dtype=torch.float64)
-    _lib.check(_lib.lib().rdn_report_value(ctypes.cast(h.data_ptr(), ctypes.POINTER(ctypes.c_int64)), nbins,
-                                           ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_double))),
-               "rdn_report_value")
-    return out
+    return _report_value(report, nbins, "report", _lib.report_words, _lib.REPORT_VALUES, "rdn_report_value")
+
+
+def physics_value(report, nbins):
+    """Doubles of a PhysicsAwareLoss report (float64 (nbins + 3, 7), CPU): one row per report row --
+    underflow, the bins, overflow -- then the totals over all of them; columns {count, ΣMSE, ΣSmooth, ΣPeak,
+    ΣNoise, ΣTotal, ΣPeakCount}.  Each sum is the exact total rounded once, NaN where a value was out of
+    range (rdn_physics_value)."""
+    return _report_value(report, nbins, "physics report", _lib.phys_words, _lib.PHYS_VALUES, "rdn_physics_value")
+
+
+def _report_args(x, y, clean, short, key, bins, report, words, unbinned, per_spectrum):
+    """What snr() and physics() do with their (type-checked) arguments before the launch: x, y, clean as
+    (n, L) rows of one shape on one device, and -- with ``bins`` -- the fp32 edges, the report of
+    ``words``(nbins) int64 (made when None) and the key.  ``short`` = (least L, its message);
+    ``unbinned``: the message if report inputs were given without ``bins``, else None.
+    Returns (x, y, clean, n, L, device, lo, hi, nbins, report)."""
+    x, y, clean = _rows(x), _rows(y), _rows(clean)
+    if x.shape != y.shape or y.shape != clean.shape:
+        raise ValueError(f"shape mismatch {tuple(x.shape)} vs {tuple(y.shape)} vs {tuple(clean.shape)}")
+    n, L = y.shape
+    if L < short[0]:
+        raise ValueError(short[1])
+    dev = y.device
+    if x.device != dev or clean.device != dev:
+        raise ValueError(f"denoised on {dev} but input on {x.device} and clean on {clean.device}")
+    if bins is None:
+        if unbinned is not None:
+            raise ValueError(unbinned)
+        if not per_spectrum:
+            raise ValueError("nothing to compute: per_spectrum=False and no bins")
+        return x, y, clean, n, L, dev, 0.0, 0.0, 0, None
+    lo, hi, nbins = _bins(bins)
+    if report is None:
+        report = _new_report(nbins, dev, words)
+    else:
+        _check_out(report, "report", (words(nbins),), dev, torch.int64)
+    if key is not None:
+        _check_out(key, "key", (n,), dev, torch.float32)
+    return x, y, clean, n, L, dev, lo, hi, nbins, report
 
 
 def snr(x, y, clean, key=None, bins=None, per4=None, report=None, per_spectrum=True):
@@ -542,82 +614,17 @@ def snr(x, y, clean, key=None, bins=None, per4=None, report=None, per_spectrum=T
     Returns (per (n, 3) or None, report or None)."""
     _check_cuda_f32(x, "input")
     _check_cuda_f32(y, "denoised")
-    if not (torch.is_tensor(clean) and clean.is_cuda):
-        raise RuntimeError("raman_mi355x runs on the GPU only: clean must be a CUDA (HIP) tensor")
-    if clean.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"clean must be float32 or float64, got {clean.dtype}")
-    x, y, clean = _rows(x), _rows(y), _rows(clean)
-    if x.shape != y.shape or y.shape != clean.shape:
-        raise ValueError(f"shape mismatch {tuple(x.shape)} vs {tuple(y.shape)} vs {tuple(clean.shape)}")
-    n, L = y.shape
-    if L < 1:
-        raise ValueError("spectra must have at least one sample")
-    dev = y.device
-    if x.device != dev or clean.device != dev:
-        raise ValueError(f"denoised on {dev} but input on {x.device} and clean on {clean.device}")
-    if bins is None:
-        if key is not None or per4 is not None or report is not None:
-            raise ValueError("key, per4 and report feed the binned report: pass bins=(lo, hi, nbins)")
-        if not per_spectrum:
-            raise ValueError("nothing to compute: per_spectrum=False and no bins")
-        lo = hi = 0.0
-        nbins = 0
-    else:
-        lo, hi, nbins = _bins(bins)
-        if report is None:
-            report = new_report(nbins, dev)
-        else:
-            _check_out(report, "report", (_lib.report_words(nbins),), dev, torch.int64)
-        if key is not None:
-            _check_out(key, "key", (n,), dev, torch.float32)
-        if per4 is not None:
-            _check_out(per4, "per4", (n, 4), dev, torch.float64)
+    _check_clean(clean)
+    fed = key is not None or per4 is not None or report is not None
+    x, y, clean, n, L, dev, lo, hi, nbins, report = _report_args(
+        x, y, clean, (1, "spectra must have at least one sample"), key, bins, report, _lib.report_words,
+        "key, per4 and report feed the binned report: pass bins=(lo, hi, nbins)" if fed else None, per_spectrum)
+    if per4 is not None:
+        _check_out(per4, "per4", (n, 4), dev, torch.float64)
     per = torch.empty((n, 3), dtype=torch.float64, device=dev) if per_spectrum else None
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-    _lib.check(_lib.lib().rdn_snr(ptr(x), ptr(y), ptr(clean), int(clean.dtype == torch.float64), n, L, ptr(per),
-                                  ptr(key), lo, hi, nbins, ptr(per4), ptr(report), _stream(dev)), "rdn_snr")
+    _lib.check(_lib.lib().rdn_snr(_ptr(x), _ptr(y), _ptr(clean), int(clean.dtype == torch.float64), n, L, _ptr(per),
+                                  _ptr(key), lo, hi, nbins, _ptr(per4), _ptr(report), _stream(dev)), "rdn_snr")
     return per, report
-
-
-# ---- PhysicsAwareLoss report (rdn_physics; definitions and report layout: include/raman_mi355x.h) ----
-PHYS_QUANTITIES = ("MSE", "Smooth", "Peak", "Noise", "Total", "PeakCount")
-PHYS_WEIGHTS = (0.1, 0.05, 0.01)          # PIDN/train.py:112 alpha, beta, gamma
-
-
-def _weights(weights):
-    """(alpha, beta, gamma) as rdn_physics takes them: three finite floats."""
-    try:
-        a, b, g = (float(w) for w in weights)
-    except (TypeError, ValueError):
-        raise ValueError(f"weights must be (alpha, beta, gamma), got {weights!r}") from None
-    if not all(abs(w) < float("inf") for w in (a, b, g)):          # NaN fails the comparison too
-        raise ValueError(f"weights must be finite, got {(a, b, g)}")
-    return a, b, g
-
-
-def new_physics_report(nbins, device):
-    """A zeroed PhysicsAwareLoss report (RDN_PHYS_WORDS(nbins) int64: nbins + 2 rows) on ``device``."""
-    if isinstance(nbins, bool) or int(nbins) != nbins or not 1 <= int(nbins) <= _lib.REPORT_MAX_BINS:
-        raise ValueError(f"nbins must be an integer in [1, {_lib.REPORT_MAX_BINS}], got {nbins!r}")
-    return torch.zeros(_lib.phys_words(int(nbins)), dtype=torch.int64, device=device)
-
-
-def physics_value(report, nbins):
-    """Doubles of a PhysicsAwareLoss report (float64 (nbins + 3, 7), CPU): one row per report row --
-    underflow, the bins, overflow -- then the totals over all of them; columns {count, ΣMSE, ΣSmooth, ΣPeak,
-    ΣNoise, ΣTotal, ΣPeakCount}.  Each sum is the exact total rounded once, NaN where a value was out of
-    range (rdn_physics_value)."""
-    nbins = int(nbins)
-    if not 1 <= nbins <= _lib.REPORT_MAX_BINS:
-        raise ValueError(f"nbins must be in [1, {_lib.REPORT_MAX_BINS}], got {nbins}")
-    h = report.detach().to("cpu", torch.int64).contiguous()
-    if h.numel() != _lib.phys_words(nbins):
-        raise ValueError(f"a physics report of {nbins} bins has {_lib.phys_words(nbins)} words, got {h.numel()}")
-    out = torch.empty((_lib.report_rows(nbins) + 1, _lib.PHYS_VALUES), dtype=torch.float64)
-    _lib.check(_lib.lib().rdn_physics_value(ctypes.cast(h.data_ptr(), ctypes.POINTER(ctypes.c_int64)), nbins,
-                                            ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_double))),
-               "rdn_physics_value")
-    return out
 
 
 def physics(x, y, clean, weights=PHYS_WEIGHTS, key=None, bins=None, report=None, per_spectrum=True):
@@ -631,37 +638,14 @@ def physics(x, y, clean, weights=PHYS_WEIGHTS, key=None, bins=None, report=None,
     None)."""
     _check_cuda_f32(x, "input")
     _check_cuda_f32(y, "denoised")
-    if not (torch.is_tensor(clean) and clean.is_cuda):
-        raise RuntimeError("raman_mi355x runs on the GPU only: clean must be a CUDA (HIP) tensor")
-    if clean.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"clean must be float32 or float64, got {clean.dtype}")
+    _check_clean(clean)
     alpha, beta, gamma = _weights(weights)
-    x, y, clean = _rows(x), _rows(y), _rows(clean)
-    if x.shape != y.shape or y.shape != clean.shape:
-        raise ValueError(f"shape mismatch {tuple(x.shape)} vs {tuple(y.shape)} vs {tuple(clean.shape)}")
-    n, L = y.shape
-    if L < 3:
-        raise ValueError("spectra must have at least three samples (the peak term is a mean over L - 2)")
-    dev = y.device
-    if x.device != dev or clean.device != dev:
-        raise ValueError(f"denoised on {dev} but input on {x.device} and clean on {clean.device}")
-    if bins is None:
-        if key is not None or report is not None:
-            raise ValueError("key and report belong to the binned report: pass bins=(lo, hi, nbins)")
-        if not per_spectrum:
-            raise ValueError("nothing to compute: per_spectrum=False and no bins")
-        lo = hi = 0.0
-        nbins = 0
-    else:
-        lo, hi, nbins = _bins(bins)
-        if report is None:
-            report = new_physics_report(nbins, dev)
-        else:
-            _check_out(report, "report", (_lib.phys_words(nbins),), dev, torch.int64)
-        if key is not None:
-            _check_out(key, "key", (n,), dev, torch.float32)
+    fed = key is not None or report is not None
+    x, y, clean, n, L, dev, lo, hi, nbins, report = _report_args(
+        x, y, clean, (3, "spectra must have at least three samples (the peak term is a mean over L - 2)"), key, bins,
+        report, _lib.phys_words, "key and report belong to the binned report: pass bins=(lo, hi, nbins)" if fed else None,
+        per_spectrum)
     per = torch.empty((n, 6), dtype=torch.float64, device=dev) if per_spectrum else None
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-    _lib.check(_lib.lib().rdn_physics(ptr(x), ptr(y), ptr(clean), int(clean.dtype == torch.float64), n, L, alpha, beta,
-                                      gamma, ptr(per), ptr(key), lo, hi, nbins, ptr(report), _stream(dev)), "rdn_physics")
+    _lib.check(_lib.lib().rdn_physics(_ptr(x), _ptr(y), _ptr(clean), int(clean.dtype == torch.float64), n, L, alpha, beta,
+                                      gamma, _ptr(per), _ptr(key), lo, hi, nbins, _ptr(report), _stream(dev)), "rdn_physics")
     return per, report

@@ -63,13 +63,20 @@ SNR_KEYS = ("SNR_in", "SNR_out", "SNR_gain")
 _SNR_RESULT_KEYS = SNR_KEYS + ("by_snr", "snr_under", "snr_over")
 
 
+def _bin_rows(v, bins):
+    """(row, lo, hi) of a *_value table ``v`` for the underflow row, each bin with its edges, the overflow row."""
+    lo, hi, nbins = engine._bins(bins)
+    edges = [float("-inf")] + np.linspace(np.float64(lo), np.float64(hi), nbins + 1).tolist() + [float("inf")]
+    return [(v[r], edges[r], edges[r + 1]) for r in range(nbins + 2)]
+
+
 def snr_summary(report, bins):
     """What ``snr_bins`` adds to a result, from an (all-reduced) report: the means of SNR_in, SNR_out and
     SNR_gain over all spectra (dB), and ``by_snr``: one entry per bin with its edges ``lo`` / ``hi``, its
     ``count`` and -- unless the bin is empty -- the seven means (the four metrics only where per-spectrum
     metrics were supplied).  ``snr_under`` / ``snr_over`` are the same entries for keys below ``lo`` and
     at or above ``hi`` (or NaN).  A mean over values that include a non-finite one is NaN."""
-    lo, hi, nbins = engine._bins(bins)
+    nbins = engine._bins(bins)[2]
     v = engine.report_value(report, nbins).tolist()
 
     def entry(row, e_lo, e_hi):
@@ -81,14 +88,12 @@ def snr_summary(report, bins):
                 e[k] = row[1 + i] / c
         return e
 
-    edges = np.linspace(np.float64(lo), np.float64(hi), nbins + 1).tolist()
     total = entry(v[nbins + 2], float("-inf"), float("inf"))
     if total["count"] <= 0:
         raise ValueError("no spectra were evaluated")
     out = {k: total[k] for k in SNR_KEYS}
-    out["by_snr"] = [entry(v[1 + b], edges[b], edges[b + 1]) for b in range(nbins)]
-    out["snr_under"] = entry(v[0], float("-inf"), lo)
-    out["snr_over"] = entry(v[nbins + 1], hi, float("inf"))
+    rows = [entry(*r) for r in _bin_rows(v, bins)]
+    out["by_snr"], out["snr_under"], out["snr_over"] = rows[1:-1], rows[0], rows[-1]
     return out
 
 
@@ -130,11 +135,8 @@ def physics_summary(report, weights, L, bins=None):
     if out["count"] <= 0:
         raise ValueError("no spectra were evaluated")
     if bins is not None:
-        lo, hi, _ = engine._bins(bins)
-        edges = np.linspace(np.float64(lo), np.float64(hi), nbins + 1).tolist()
-        out["by_snr"] = [entry(v[1 + b], {"lo": edges[b], "hi": edges[b + 1]}) for b in range(nbins)]
-        out["under"] = entry(v[0], {"lo": float("-inf"), "hi": lo})
-        out["over"] = entry(v[nbins + 1], {"lo": hi, "hi": float("inf")})
+        rows = [entry(row, {"lo": e_lo, "hi": e_hi}) for row, e_lo, e_hi in _bin_rows(v, bins)]
+        out["by_snr"], out["under"], out["over"] = rows[1:-1], rows[0], rows[-1]
     return out
 
 
@@ -160,6 +162,51 @@ def _workspace(model, n, L, device):
             or torch.device(device).type != "cuda"):
         return None
     return engine.Workspace(model.ARCH, model.engine_code, n, L, device)
+
+
+class _Meters:
+    """One model's exact accumulator and its optional SNR and PhysicsAwareLoss reports: the forward +
+    metrics of each batch go into ``acc`` (``per_spectrum``: the SNR report wants their per-spectrum
+    output), add() runs the batch's report passes, summary() all-reduces and summarises."""
+
+    def __init__(self, device, snr_bins, weights):
+        self.snr_bins, self.weights = snr_bins, weights
+        self.phys_bins = snr_bins if snr_bins is not None else (0.0, 1.0, 1)      # unbinned: one bin, no key
+        self.acc = engine.new_acc(device)
+        self.report = engine.new_report(engine._bins(snr_bins)[2], device) if snr_bins is not None else None
+        self.phys_rep = (engine.new_physics_report(engine._bins(self.phys_bins)[2], device)
+                         if weights is not None else None)
+        self.per_spectrum = self.report is not None
+
+    def add(self, x, y, clean, per, key):
+        """The SNR pass, then the physics pass, of a batch (``per``: its per-spectrum metrics; ``key``: its
+        nominal SNRs or None, which bins by the measured SNR_in)."""
+        if self.report is None:
+            key = None
+        else:
+            # without nominal SNRs the physics report needs the key rdn_snr bins by: its SNR_in in fp32
+            per3, _ = engine.snr(x, y, clean, key=key, bins=self.snr_bins, per4=per, report=self.report,
+                                 per_spectrum=self.phys_rep is not None and key is None)
+            if per3 is not None:
+                key = per3[:, 0].to(torch.float32).contiguous()
+        if self.phys_rep is not None:
+            engine.physics(x, y, clean, weights=self.weights, key=key, bins=self.phys_bins, report=self.phys_rep,
+                           per_spectrum=False)
+
+    def summary(self, L, words=False):
+        """All-reduce the accumulator and the reports: (means, what snr_bins / physics add to a result --
+        with ``words`` the all-reduced report words too)."""
+        means = means_from_acc(_all_reduce_acc(self.acc))
+        extra = {}
+        if self.report is not None:
+            extra.update(snr_summary(_all_reduce_acc(self.report), self.snr_bins))
+            if words:
+                extra["report"] = self.report.cpu().tolist()
+        if self.phys_rep is not None:
+            extra["physics"] = physics_summary(_all_reduce_acc(self.phys_rep), self.weights, L, self.snr_bins)
+            if words:
+                extra["physics"]["report"] = self.phys_rep.cpu().tolist()
+        return means, extra
 
 
 def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bins=None, snrs=None, physics=None):
@@ -190,19 +237,13 @@ def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bi
     if device.type != "cuda":
         raise RuntimeError("raman_mi355x.evaluate runs its metrics on the GPU; on a CPU device use the module "
                            "itself in the reference's evaulate.py loop (its forward falls back to eager PyTorch)")
-    acc = engine.new_acc(device)
-    report = None
-    if snr_bins is not None:
-        report = engine.new_report(engine._bins(snr_bins)[2], device)
-        if snrs is not None:
-            snrs = torch.as_tensor(np.asarray(snrs.cpu() if torch.is_tensor(snrs) else snrs), dtype=torch.float32).reshape(-1)
-            if snrs.numel() != noisy.shape[0]:
-                raise ValueError(f"snrs has {snrs.numel()} values for {noisy.shape[0]} spectra")
-    elif snrs is not None:
-        raise ValueError("snrs is the binning key of the SNR report: pass snr_bins=(lo, hi, nbins)")
-    weights = _physics_weights(physics)
-    phys_bins = snr_bins if snr_bins is not None else (0.0, 1.0, 1)      # unbinned: one bin, no key
-    phys_rep = engine.new_physics_report(engine._bins(phys_bins)[2], device) if weights is not None else None
+    m = _Meters(device, snr_bins, _physics_weights(physics))
+    if snrs is not None:
+        if snr_bins is None:
+            raise ValueError("snrs is the binning key of the SNR report: pass snr_bins=(lo, hi, nbins)")
+        snrs = torch.as_tensor(np.asarray(snrs.cpu() if torch.is_tensor(snrs) else snrs), dtype=torch.float32).reshape(-1)
+        if snrs.numel() != noisy.shape[0]:
+            raise ValueError(f"snrs has {snrs.numel()} values for {noisy.shape[0]} spectra")
     ws = _workspace(model, min(batch_size, max(hi - lo, 1)), L, device)
     # fp64 clean stays fp64 (the metrics compare against the same float64 values as evaulate.py)
     cdt = torch.float64 if (clean.dtype == torch.float64 if torch.is_tensor(clean) else clean.dtype == np.float64) \
@@ -215,28 +256,14 @@ def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bi
             if _engine_module(model) and model.uses_engine(x):
                 # the engine's forward + metric sums (fused into the forward kernel on the walk geometry)
                 y, per, _, _ = engine.forward_metrics(model.ARCH, model.engine_code, model.packed_weights(x.device), x, c,
-                                                      acc=acc, per_spectrum=report is not None, check=False, workspace=ws)
+                                                      acc=m.acc, per_spectrum=m.per_spectrum, check=False, workspace=ws)
             else:
                 y = model(x)
-                per, _ = engine.metrics(y.squeeze(1), c, per_spectrum=report is not None, acc=acc)
-            if report is not None:
-                key = snrs[b0:b1].to(device) if snrs is not None else None
-                # without nominal SNRs the physics report needs the key rdn_snr bins by: its SNR_in in fp32
-                per3, _ = engine.snr(x, y, c, key=key, bins=snr_bins, per4=per, report=report,
-                                     per_spectrum=phys_rep is not None and key is None)
-                if per3 is not None:
-                    key = per3[:, 0].to(torch.float32).contiguous()
-            else:
-                key = None
-            if phys_rep is not None:
-                engine.physics(x, y, c, weights=weights, key=key, bins=phys_bins, report=phys_rep, per_spectrum=False)
+                per, _ = engine.metrics(y.squeeze(1), c, per_spectrum=m.per_spectrum, acc=m.acc)
+            m.add(x, y, c, per, snrs[b0:b1].to(device) if snrs is not None else None)
     _finish(model, ws)
-    _all_reduce_acc(acc)
-    means = means_from_acc(acc)
-    if report is not None:
-        means.update(snr_summary(_all_reduce_acc(report), snr_bins))
-    if phys_rep is not None:
-        means["physics"] = physics_summary(_all_reduce_acc(phys_rep), weights, L, snr_bins)
+    means, extra = m.summary(L)
+    means.update(extra)
     return means
 
 
@@ -263,7 +290,6 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
     device = torch.device(device)
     gen_kwargs = gen_kwargs or {}
     weights = _physics_weights(physics)
-    phys_bins = snr_bins if snr_bins is not None else (0.0, 1.0, 1)
     rank, W = world()
     lo, hi = shard(total, rank, W)
     L = int(signal_length)
@@ -275,9 +301,7 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
     with torch.no_grad():
         for name, model in models.items():
             model.eval()
-            acc = engine.new_acc(device)
-            report = engine.new_report(engine._bins(snr_bins)[2], device) if snr_bins is not None else None
-            phys_rep = engine.new_physics_report(engine._bins(phys_bins)[2], device) if weights is not None else None
+            m = _Meters(device, snr_bins, weights)
             ws = _workspace(model, B, L, device)
             packed = model.packed_weights(device)
             if dist.is_available() and dist.is_initialized():
@@ -299,19 +323,13 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
                 # spectrum itself (no second pass over y); otherwise the metrics kernel follows it
                 if fused_metrics:
                     _, per, _, _ = engine.forward_metrics(model.ARCH, model.engine_code, packed, noisy[:nb].view(nb, 1, L),
-                                                          clean[:nb], out=y[:nb], acc=acc, per_spectrum=report is not None,
+                                                          clean[:nb], out=y[:nb], acc=m.acc, per_spectrum=m.per_spectrum,
                                                           check=False, workspace=ws)
                 else:
                     engine.forward(model.ARCH, model.engine_code, packed, noisy[:nb].view(nb, 1, L), out=y[:nb],
                                    check=False, workspace=ws)
-                    per, _ = engine.metrics(y[:nb].view(nb, L), clean[:nb], per_spectrum=report is not None, acc=acc)
-                if report is not None:
-                    engine.snr(noisy[:nb], y[:nb], clean[:nb], key=snr_db, bins=snr_bins, per4=per, report=report,
-                               per_spectrum=False)
-                if phys_rep is not None:
-                    engine.physics(noisy[:nb], y[:nb], clean[:nb], weights=weights,
-                                   key=snr_db if snr_bins is not None else None, bins=phys_bins, report=phys_rep,
-                                   per_spectrum=False)
+                    per, _ = engine.metrics(y[:nb].view(nb, L), clean[:nb], per_spectrum=m.per_spectrum, acc=m.acc)
+                m.add(noisy[:nb], y[:nb], clean[:nb], per, snr_db)       # binned by the generator's nominal SNR
             _finish(model, ws)              # waits for the stream; raises on a timed-out hand-off / range / gate
             torch.cuda.synchronize(device)
             el = time.perf_counter() - t0
@@ -320,18 +338,10 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
                 tt = t.to(device) if dist.get_backend() != "gloo" else t
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
                 t = tt.cpu()
-            _all_reduce_acc(acc)
+            means, extra = m.summary(L, words=True)
             el = float(t.item())
-            out[name] = {"means": means_from_acc(acc), "acc": acc.cpu().tolist(), "spectra": int(total),
-                         "seconds": el, "spectra_per_s": total / el if el > 0 else None}
-            if report is not None:
-                _all_reduce_acc(report)
-                out[name].update(snr_summary(report, snr_bins))
-                out[name]["report"] = report.cpu().tolist()
-            if phys_rep is not None:
-                _all_reduce_acc(phys_rep)
-                out[name]["physics"] = physics_summary(phys_rep, weights, L, snr_bins)
-                out[name]["physics"]["report"] = phys_rep.cpu().tolist()
+            out[name] = {"means": means, "acc": m.acc.cpu().tolist(), "spectra": int(total),
+                         "seconds": el, "spectra_per_s": total / el if el > 0 else None, **extra}
     return out
 
 
@@ -345,6 +355,15 @@ def write_metrics(metrics, root="eval_results"):
             if k not in _EXTRA_RESULT_KEYS:
                 f.write(f"{k}: {v:.6f}\n")
     return save_dir
+
+
+def _write_table(f, cols, entries, fmt):
+    """One line per entry (a summary's under / by_snr / over): its edges, its count and ``cols`` ('-' for a
+    mean an empty bin does not have)."""
+    f.write("lo hi count " + " ".join(cols) + "\n")
+    for e in entries:
+        f.write(f"{e['lo']:.4f} {e['hi']:.4f} {e['count']} "
+                + " ".join(format(e[k], fmt) if k in e else "-" for k in cols) + "\n")
 
 
 def write_snr_report(result, root):
@@ -362,10 +381,7 @@ def write_snr_report(result, root):
     with open(os.path.join(root, "snr_report.txt"), "w") as f:
         for k in SNR_KEYS:
             f.write(f"{k}: {result[k]:.6f}\n")
-        f.write("lo hi count " + " ".join(cols) + "\n")
-        for e in [result["snr_under"]] + list(result["by_snr"]) + [result["snr_over"]]:
-            f.write(f"{e['lo']:.4f} {e['hi']:.4f} {e['count']} "
-                    + " ".join(f"{e[k]:.6f}" if k in e else "-" for k in cols) + "\n")
+        _write_table(f, cols, [result["snr_under"]] + list(result["by_snr"]) + [result["snr_over"]], ".6f")
     return root
 
 
@@ -387,8 +403,5 @@ def write_physics_report(result, root):
         for k in cols:
             f.write(f"{k}: {part[k]:.6e}\n")
         if "by_snr" in part:
-            f.write("lo hi count " + " ".join(cols) + "\n")
-            for e in [part["under"]] + list(part["by_snr"]) + [part["over"]]:
-                f.write(f"{e['lo']:.4f} {e['hi']:.4f} {e['count']} "
-                        + " ".join(f"{e[k]:.6e}" if k in e else "-" for k in cols) + "\n")
+            _write_table(f, cols, [part["under"]] + list(part["by_snr"]) + [part["over"]], ".6e")
     return root

@@ -34,6 +34,8 @@ import math
 
 import numpy as np
 
+import exact_acc
+
 WIN = 7
 FIX = 320            # fractional bits of the SSIM sum's fixed-point bracket
 
@@ -174,18 +176,11 @@ def ssim_err(got, exact):
         return np.where(noise, np.abs(got - exact), rel_err(got, np.where(noise, 1.0, exact)))
 
 
-def acc_words(per, acc_of, limbs, stride):
+def acc_words(per):
     """The exact accumulator (int64 words, RDN_ACC_WORDS) that the per-spectrum values ``per`` (n, 4) give:
     a value that is not finite or is >= 2^64 in magnitude counts in its metric's out-of-range word, every
-    other one goes through ``acc_of`` (tests/test_abi.py _acc_of, the host restatement of to_limbs)."""
-    per = np.asarray(per, np.float64)
-    words = [0] * (4 * stride + 1)
-    for k in range(4):
-        ok = np.isfinite(per[:, k]) & (np.abs(per[:, k]) < 2.0 ** 64)
-        words[k * stride: k * stride + limbs] = acc_of([float(v) for v in per[ok, k]])
-        words[k * stride + limbs] = int((~ok).sum())
-    words[4 * stride] = per.shape[0]
-    return words
+    other one goes into its limbs (exact_acc.row_words, the host restatement of the device's accumulator)."""
+    return exact_acc.row_words(per).tolist()
 
 
 # ---- the input families of the metric domain tests (CPU: oracle against arbiter; GPU: device against arbiter) ----

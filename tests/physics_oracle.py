@@ -1,15 +1,14 @@
 """Plain-numpy oracle of the PhysicsAwareLoss report (include/raman_mi355x.h rdn_physics): float64 for
 the values, clean's own type for the mask, exact (math.fsum) sums for a report.  Shared by
 test_physics_cpu.py and test_physics_gpu.py."""
-import math
-
 import numpy as np
 
-import snr_oracle as S
+import exact_acc as E
+from exact_acc import report_sums, report_words  # noqa: F401  (one count word per row: the defaults)
 
 QUANTITIES = ("MSE", "Smooth", "Peak", "Noise", "Total", "PeakCount")
 WEIGHTS = (0.1, 0.05, 0.01)
-ACC_LIMBS, ACC_STRIDE = S.ACC_LIMBS, S.ACC_STRIDE
+ACC_LIMBS, ACC_STRIDE = E.ACC_LIMBS, E.ACC_STRIDE
 ROW_WORDS = 6 * ACC_STRIDE + 1
 COUNT = 6 * ACC_STRIDE
 
@@ -43,30 +42,3 @@ def physics_values(x, y, clean, weights=WEIGHTS, dtype=np.float64):
         noise = np.sum((d * d - v) ** 2, axis=1) / L
         total = ((mse + alpha * smooth) + beta * peak) + gamma * noise
     return np.stack([mse, smooth, peak, noise, total, np.sum(m, axis=1)], axis=1)
-
-
-def report_words(per6, rows, nbins):
-    """The int64 words of the report of spectra with the six values per6 (n, 6) in report rows `rows`."""
-    rep = np.zeros((nbins + 2, ROW_WORDS), dtype=np.int64)
-    for b in range(nbins + 2):
-        sel = per6[rows == b]
-        rep[b, COUNT] = len(sel)
-        for k in range(6):
-            col = sel[:, k]
-            ok = np.array([S.in_range(v) for v in col], dtype=bool)
-            rep[b, k * ACC_STRIDE:k * ACC_STRIDE + ACC_LIMBS] = S.limbs_of(col[ok])
-            rep[b, k * ACC_STRIDE + ACC_LIMBS] = int((~ok).sum())
-    return rep.reshape(-1)
-
-
-def report_sums(per6, rows, nbins):
-    """(nbins + 3, 7): per report row, then for all spectra: count and the six exact sums rounded once
-    (NaN for a quantity with a value that is not finite)."""
-    out = np.zeros((nbins + 3, 7))
-    sels = [rows == b for b in range(nbins + 2)] + [np.ones(len(rows), dtype=bool)]
-    for b, sel_mask in enumerate(sels):
-        sel = per6[sel_mask]
-        out[b, 0] = len(sel)
-        for k in range(6):
-            out[b, 1 + k] = math.fsum(sel[:, k]) if all(S.in_range(v) for v in sel[:, k]) else float("nan")
-    return out

@@ -1,12 +1,12 @@
 """Plain-numpy oracle of the SNR report (include/raman_mi355x.h rdn_snr): float64 for the values,
 float32 for the bin index, exact (math.fsum) sums.  Shared by test_snr_cpu.py and test_snr_gpu.py."""
-import math
-from fractions import Fraction
-
 import numpy as np
 
+import exact_acc as E
+from exact_acc import in_range, limbs_of, report_sums  # noqa: F401  (the names the tests have always used)
+
 QUANTITIES = ("MSE", "SSIM", "Smoothness", "Peak2Peak", "SNR_in", "SNR_out", "SNR_gain")
-ACC_LIMBS, ACC_STRIDE, FRAC_BITS = 6, 7, 128
+ACC_LIMBS, ACC_STRIDE, FRAC_BITS = E.ACC_LIMBS, E.ACC_STRIDE, E.FRAC_BITS
 ROW_WORDS = 7 * ACC_STRIDE + 2
 COUNT, COUNT4 = 7 * ACC_STRIDE, 7 * ACC_STRIDE + 1
 
@@ -37,45 +37,6 @@ def bin_rows(key, lo, hi, nbins):
     return rows.astype(np.int64)
 
 
-def limbs_of(values):
-    """Host restatement of the device accumulator (metrics.hpp to_limbs) for finite |v| < 2^64."""
-    limbs = [0] * ACC_LIMBS
-    for v in values:
-        f = Fraction(float(v)) * 2 ** FRAC_BITS
-        mag = abs(f.numerator) // f.denominator                    # truncation toward zero
-        for j in range(ACC_LIMBS):
-            c = (mag >> (32 * j)) & 0xffffffff
-            limbs[j] += -c if v < 0 else c
-    return limbs
-
-
-def in_range(v):
-    return math.isfinite(v) and abs(v) < 2.0 ** 64
-
-
 def report_words(per7, rows, nbins, have4=True):
     """The int64 words of the report of spectra with the seven values per7 (n, 7) in report rows `rows`."""
-    rep = np.zeros((nbins + 2, ROW_WORDS), dtype=np.int64)
-    for b in range(nbins + 2):
-        sel = per7[rows == b]
-        rep[b, COUNT] = len(sel)
-        rep[b, COUNT4] = len(sel) if have4 else 0
-        for k in range(0 if have4 else 4, 7):
-            col = sel[:, k]
-            ok = np.array([in_range(v) for v in col], dtype=bool)
-            rep[b, k * ACC_STRIDE:k * ACC_STRIDE + ACC_LIMBS] = limbs_of(col[ok])
-            rep[b, k * ACC_STRIDE + ACC_LIMBS] = int((~ok).sum())
-    return rep.reshape(-1)
-
-
-def report_sums(per7, rows, nbins):
-    """(nbins + 3, 8): per report row, then for all spectra: count and the seven exact sums rounded once
-    (NaN for a quantity with a value that is not finite)."""
-    out = np.zeros((nbins + 3, 8))
-    sels = [rows == b for b in range(nbins + 2)] + [np.ones(len(rows), dtype=bool)]
-    for b, m in enumerate(sels):
-        sel = per7[m]
-        out[b, 0] = len(sel)
-        for k in range(7):
-            out[b, 1 + k] = math.fsum(sel[:, k]) if all(in_range(v) for v in sel[:, k]) else float("nan")
-    return out
+    return E.report_words(per7, rows, nbins, counts=(1, int(have4)), skip=0 if have4 else 4)

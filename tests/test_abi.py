@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import ROOT, golden_state_dict
+from exact_acc import limbs_of
 
 ARCHS = ["DenoiseCNN", "RRCDNet", "DSDN", "ADSDN", "PIDN", "APIDN"]
 
@@ -121,20 +122,6 @@ def test_blob_layout_tag(lib):
             engine.check_blob(arch, dt, engine.pack(arch, golden_state_dict(arch, "synth"), dt, "cpu"))
 
 
-def _acc_of(values):
-    """Host restatement of the device accumulator (metrics.hip to_limbs): limbs of one metric."""
-    from fractions import Fraction
-    from raman_mi355x import _lib
-    limbs = [0] * _lib.ACC_LIMBS
-    for v in values:
-        f = Fraction(v) * 2 ** _lib.ACC_FRAC_BITS
-        mag = abs(f.numerator) // f.denominator                    # truncation toward zero
-        for j in range(_lib.ACC_LIMBS):
-            c = (mag >> (32 * j)) & 0xffffffff
-            limbs[j] += -c if v < 0 else c
-    return limbs
-
-
 def test_exact_accumulator_rounds_the_exact_sum_once(lib):
     """rdn_acc_value: the exact total of the (2^-128-truncated) values, rounded once to double --
     independent of summation order (the reason config-4 sums are identical for any world size)."""
@@ -145,7 +132,7 @@ def test_exact_accumulator_rounds_the_exact_sum_once(lib):
                             [1e-40, -3e-39, 2.0 ** 63, -(2.0 ** 62), 0.1, 0.2, 0.3]]) for _ in range(4)]
     acc = torch.zeros(_lib.ACC_WORDS, dtype=torch.int64)
     for k in range(4):
-        acc[k * _lib.ACC_STRIDE: k * _lib.ACC_STRIDE + _lib.ACC_LIMBS] = torch.tensor(_acc_of(vals[k]))
+        acc[k * _lib.ACC_STRIDE: k * _lib.ACC_STRIDE + _lib.ACC_LIMBS] = torch.tensor(limbs_of(vals[k]))
     acc[_lib.ACC_COUNT] = 507
     out = engine.acc_value(acc).numpy()
     for k in range(4):
@@ -154,6 +141,31 @@ def test_exact_accumulator_rounds_the_exact_sum_once(lib):
     assert out[4] == 507
     acc[_lib.ACC_LIMBS] = 1                                          # an out-of-range value in metric 0
     assert np.isnan(engine.acc_value(acc).numpy()[0])
+
+
+@pytest.mark.parametrize("nbins", [1, 64])
+def test_report_conversions_are_the_fsum_oracle(lib, nbins):
+    """rdn_report_value and rdn_physics_value are one conversion over two row layouts (abi.cpp
+    acc_rows_value): at the fewest and the most bins, every row's counts and sums and the totals row are
+    the math.fsum oracle's -- equal, not close: the values are multiples of 2^-73, far above the limbs'
+    2^-128, so both round the same exact sum once -- and the row holding a value that is out of range, and
+    the totals, are NaN for that quantity alone."""
+    import exact_acc as E
+    from raman_mi355x import engine, _lib
+    rng = np.random.default_rng(nbins)
+    n = 40 * (nbins + 2)
+    rows = rng.permutation(np.arange(n) % (nbins + 2))
+    for q, counts, value in ((7, (1, 1), engine.report_value), (6, (1,), engine.physics_value)):
+        per = rng.uniform(-1, 1, (n, q)) * 2.0 ** rng.integers(-20, 21, (n, q))
+        bad = int(np.flatnonzero(rows == nbins)[0])                   # a spectrum of the last bin
+        per[bad, q - 2] = np.inf
+        got = value(torch.from_numpy(E.report_words(per, rows, nbins, counts)), nbins).numpy()
+        ref = E.report_sums(per, rows, nbins)
+        assert got.shape == (nbins + 3, 1 + q + len(counts) - 1)
+        np.testing.assert_array_equal(got[:, :1 + q], ref)
+        assert np.array_equal(got[:, 1 + q:], np.repeat(ref[:, :1], len(counts) - 1, axis=1))
+        nan = np.argwhere(np.isnan(got)).tolist()
+        assert nan == [[nbins, q - 1], [nbins + 2, q - 1]]
 
 
 def test_forward_status_without_gpu_reports_error_not_crash(lib):

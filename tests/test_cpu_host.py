@@ -302,12 +302,12 @@ def _acc_worker(rank, world, port, per, out):
     import torch.distributed as dist
     from raman_mi355x import _lib, engine
     from raman_mi355x.distributed import shard
-    from test_abi import _acc_of
+    from exact_acc import limbs_of
     dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
     lo, hi = shard(per.shape[0])
     acc = torch.zeros(_lib.ACC_WORDS, dtype=torch.int64)
     for k in range(4):
-        acc[k * _lib.ACC_STRIDE: k * _lib.ACC_STRIDE + _lib.ACC_LIMBS] = torch.tensor(_acc_of(per[lo:hi, k]))
+        acc[k * _lib.ACC_STRIDE: k * _lib.ACC_STRIDE + _lib.ACC_LIMBS] = torch.tensor(limbs_of(per[lo:hi, k]))
     acc[_lib.ACC_COUNT] = hi - lo
     dist.all_reduce(acc, op=dist.ReduceOp.SUM)
     if rank == 0:
@@ -322,12 +322,12 @@ def test_exact_accumulator_allreduce_world2_gloo():
     import sys
     sys.path.insert(0, os.path.dirname(__file__))
     from raman_mi355x import _lib, engine
-    from test_abi import _acc_of
+    from exact_acc import limbs_of
     g = np.load(os.path.join(GOLDEN, "metrics.npz"))
     per = g["per_spectrum"].astype(np.float64)
     acc = torch.zeros(_lib.ACC_WORDS, dtype=torch.int64)
     for k in range(4):
-        acc[k * _lib.ACC_STRIDE: k * _lib.ACC_STRIDE + _lib.ACC_LIMBS] = torch.tensor(_acc_of(per[:, k]))
+        acc[k * _lib.ACC_STRIDE: k * _lib.ACC_STRIDE + _lib.ACC_LIMBS] = torch.tensor(limbs_of(per[:, k]))
     acc[_lib.ACC_COUNT] = per.shape[0]
     one = engine.acc_value(acc).tolist()
     port = _free_port()

@@ -24,7 +24,6 @@ import torch
 from conftest import golden_state_dict
 from metrics_exact import (FAMILY_NAMES, _ratio, acc_words, exact_per_spectrum, exact_total, family_table, rel_err,
                            ssim_err)
-from test_abi import _acc_of
 
 pytestmark = pytest.mark.gpu
 
@@ -37,8 +36,7 @@ def _lib():
 
 
 def _expected_acc(per):
-    L = _lib()
-    return acc_words(per, _acc_of, L.ACC_LIMBS, L.ACC_STRIDE)
+    return acc_words(per)
 
 
 def _oor(acc):
