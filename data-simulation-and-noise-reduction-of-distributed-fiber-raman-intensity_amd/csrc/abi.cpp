@@ -564,8 +564,37 @@ int rdn_physics(const float* x, const float* y, const void* clean, int clean_is_
   if (rc != RDN_OK || n == 0) return rc;
   const rdn::phys::PhysOut po{per_spectrum6, key, (long long*)report,
                               report ? rdn::make_bins(lo, hi, nbins) : rdn::Bins{0.f, 0.f, 0.f, 0},
-                              alpha, beta, gamma};
+                              alpha, beta, gamma, nullptr, 0.0};
   return hip_check(rdn::launch_physics(x, y, clean, clean_is_f64 == 1, n, (int)L, po, (hipStream_t)stream), "physics");
+  RDN_GUARD_END
+}
+
+int rdn_physics_grad(const float* x, const float* y, const void* clean, int clean_is_f64, int64_t n, int64_t L,
+                     double alpha, double beta, double gamma, double scale, double* per_spectrum6, float* grad,
+                     void* stream) {
+  RDN_GUARD_BEGIN
+  const std::string fn = "rdn_physics_grad";
+  if (n > 0 && !(y && clean && grad)) return fail(RDN_EINVAL, fn + ": null pointer");
+  if (n > 0 && per_spectrum6 && !x) return fail(RDN_EINVAL, fn + ": per_spectrum6 needs x, which is NULL");
+  if (clean_is_f64 != 0 && clean_is_f64 != 1) return fail(RDN_EINVAL, fn + ": clean_is_f64 must be 0 or 1");
+  if (n < 0 || L < 3 || L > 0x7fffffff) return fail(RDN_EINVAL, fn + ": need n >= 0 and 3 <= L < 2^31");
+  if (!(std::isfinite(alpha) && std::isfinite(beta) && std::isfinite(gamma)))
+    return fail(RDN_EINVAL, fn + ": the weights alpha, beta, gamma must be finite");
+  if (!std::isfinite(scale)) return fail(RDN_EINVAL, fn + ": scale must be finite");
+  if (n == 0) return RDN_OK;
+  {  // every position reads its neighbours while other lanes' gradients land
+    const uintptr_t rows = (uintptr_t)n * (uintptr_t)L, gb = (uintptr_t)grad, gbytes = rows * sizeof(float);
+    const auto overlaps = [&](const void* p, uintptr_t bytes) {
+      return p && (uintptr_t)p < gb + gbytes && gb < (uintptr_t)p + bytes;
+    };
+    if (overlaps(x, rows * sizeof(float)) || overlaps(y, rows * sizeof(float)) ||
+        overlaps(clean, rows * (clean_is_f64 ? sizeof(double) : sizeof(float))))
+      return fail(RDN_EINVAL, fn + ": grad overlaps x, y or clean");
+  }
+  const rdn::phys::PhysOut po{per_spectrum6, nullptr, nullptr, rdn::Bins{0.f, 0.f, 0.f, 0}, alpha, beta, gamma, grad, scale};
+  return hip_check(rdn::launch_physics(per_spectrum6 ? x : nullptr, y, clean, clean_is_f64 == 1, n, (int)L, po,
+                                       (hipStream_t)stream),
+                   "physics_grad");
   RDN_GUARD_END
 }
 

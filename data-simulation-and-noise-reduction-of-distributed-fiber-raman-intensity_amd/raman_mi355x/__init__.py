@@ -6,7 +6,8 @@ Drop-in surfaces (reference file:line):
   generate_signals                                数据集产生.py:5-64 (simulator.py, on-device)
   evaluate, compute_*                             */evaulate.py:14-39 (evaluate.py, batched, on-device)
   evaluate(..., snr_bins=), write_snr_report      SNR_in / SNR_out / gain and the metrics by SNR bin (engine.snr)
-  PhysicsAwareLoss                                PIDN|APIDN/train.py loss class (physics.py: value on device, gradient eager)
+  PhysicsAwareLoss                                PIDN|APIDN/train.py loss class (physics.py: value on device; gradient eager,
+                                                  or from the same launch with fused_backward=True: engine.physics_grad)
   evaluate(..., physics=), write_physics_report   the loss's terms over a test set, by SNR bin (engine.physics)
 """
 from . import engine

@@ -121,6 +121,10 @@ _SIGNATURES = {
                      ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
                      ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rdn_physics_value": ([ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+    # value and gradient of PhysicsAwareLoss from one launch: likewise added to ABI v6 and detected by symbol
+    "rdn_physics_grad": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                          ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
+                          ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGNATURES)

@@ -649,3 +649,38 @@ def physics(x, y, clean, weights=PHYS_WEIGHTS, key=None, bins=None, report=None,
     _lib.check(_lib.lib().rdn_physics(_ptr(x), _ptr(y), _ptr(clean), int(clean.dtype == torch.float64), n, L, alpha, beta,
                                       gamma, _ptr(per), _ptr(key), lo, hi, nbins, _ptr(report), _stream(dev)), "rdn_physics")
     return per, report
+
+
+def physics_grad(x, y, clean, weights=PHYS_WEIGHTS, scale=None, per_spectrum=True, out=None):
+    """Value and gradient of PhysicsAwareLoss from one launch (rdn_physics_grad): the per-spectrum
+    [MSE, Smooth, Peak, Noise, Total, PeakCount] of physics() -- the same bits -- and ``grad`` = ``scale`` *
+    d Total / d ``y`` (float32, the shape of ``y``: (N, L) or (N, 1, L)).  ``scale`` = None means 1 / n: the
+    gradient of the reference's loss, the mean of Total over the batch.  ``per_spectrum`` = False computes
+    the gradient alone (no reduction, no noise passes); the noisy input ``x`` is then not read and may be
+    None.  ``out``: a float32 tensor of ``y``'s shape to write the gradient into (made when None); it must
+    not overlap x, y or clean.  Returns (per (n, 6) or None, grad)."""
+    if x is None:
+        if per_spectrum:
+            raise ValueError("the per-spectrum values need the noisy input: x=None goes with per_spectrum=False")
+    else:
+        _check_cuda_f32(x, "input")
+    _check_cuda_f32(y, "denoised")
+    _check_clean(clean)
+    alpha, beta, gamma = _weights(weights)
+    shape = tuple(y.shape)
+    x, y, clean, n, L, dev, _, _, _, _ = _report_args(
+        y if x is None else x, y, clean, (3, "spectra must have at least three samples (the peak term is a mean over L - 2)"),
+        None, None, None, _lib.phys_words, None, True)
+    if scale is None:
+        scale = 1.0 / n if n else 1.0
+    scale = float(scale)
+    if not abs(scale) < float("inf"):
+        raise ValueError(f"scale must be finite, got {scale}")
+    grad = torch.empty(shape, dtype=torch.float32, device=dev) if out is None else out
+    if out is not None:
+        _check_out(grad, "out", shape, dev)
+    per = torch.empty((n, 6), dtype=torch.float64, device=dev) if per_spectrum else None
+    _lib.check(_lib.lib().rdn_physics_grad(_ptr(x if per_spectrum else None), _ptr(y), _ptr(clean),
+                                           int(clean.dtype == torch.float64), n, L, alpha, beta, gamma, scale, _ptr(per),
+                                           _ptr(grad), _stream(dev)), "rdn_physics_grad")
+    return per, grad

@@ -370,6 +370,36 @@ int rdn_physics(const float* x, const float* y, const void* clean, int clean_is_
                 double alpha, double beta, double gamma, double* per_spectrum6, const float* key, float lo,
                 float hi, int nbins, int64_t* report, void* stream);
 
+/* ---- PhysicsAwareLoss gradient (added to ABI v6 without a version bump: detect the entry point by symbol)
+ *
+ * Value and gradient of the loss from one launch: what a training step needs (criterion(output, clean,
+ * noisy), then loss.backward()).  Per spectrum, on the stored values and in fp64 except the mask, with p,
+ * c and m_i as above (m_i exactly rdn_physics's, formed in clean's own storage type), i = 0 .. L-1:
+ *   r_i = p_i - c_i
+ *   e_i = (p_{i+1} - p_i) - (c_{i+1} - c_i)          i = 0 .. L-2
+ *   s_i = (e_i > 0) - (e_i < 0)                      0 for e_i = 0 and for NaN: torch's abs backward
+ *   g_i = scale * [ 2 r_i / L
+ *                 + alpha * (s_{i-1} [i >= 1] - s_i [i <= L-2]) / (L - 1)
+ *                 + beta * 2 m_i (m_i p_i - m_i c_i) / (L - 2)   [1 <= i <= L-2] ]
+ * rounded once to fp32.  Terms that do not exist at the row's ends are selected away, not multiplied by
+ * zero; m_i is a factor, as in the value: a non-finite p at an unmasked centre position gives NaN there,
+ * as the reference does.  A NaN at p_i gives NaN at i only (its neighbours' smoothness terms see
+ * sign(NaN) = 0); +-inf at a row's end gives +-inf there only.  gamma takes no part: the Noise term is a
+ * function of x - c alone.  With scale = 1 / n, g is d(mean over the batch of Total) / d p: the reference's
+ * loss.backward() for (N, 1, L) inputs.
+ *
+ * grad: fp32 [n][L] device, required, WRITTEN (not accumulated); it must not overlap x, y or clean (each
+ * position reads its neighbours): RDN_EINVAL.  per_spectrum6: fp64 [n][6] device or NULL, the six
+ * quantities of rdn_physics with the same bits for every spectrum (one shared device routine).  x may be
+ * NULL when per_spectrum6 is NULL: a gradient-only call reads no x and runs no reduction and no noise
+ * pass.  3 <= L < 2^31 (64-bit row offsets); alpha, beta, gamma and scale finite; scale is applied per
+ * call, whatever the number of launches a huge n is split into, so the gradient of rows [0, k) and [k, n)
+ * from two calls with one scale is the rows of one call.  n = 0 launches nothing and accepts NULL data
+ * pointers; it still checks L, the weights and scale. */
+int rdn_physics_grad(const float* x, const float* y, const void* clean, int clean_is_f64, int64_t n, int64_t L,
+                     double alpha, double beta, double gamma, double scale, double* per_spectrum6, float* grad,
+                     void* stream);
+
 /* Host: doubles of a HOST copy of a report of rdn_physics.  out: (RDN_REPORT_ROWS(nbins) + 1) rows of
  * RDN_PHYS_VALUES doubles: the report's rows in order, then the totals over all rows (their limbs added as
  * integers).  Each sum is the exact accumulated value rounded once to the nearest double, NaN for a
