@@ -13,6 +13,7 @@
 #include "host_util.hpp"
 #include "snr.hpp"
 #include "physics.hpp"
+#include "filters.hpp"
 
 namespace rdn {
 std::string pack(int arch, int dtype, const float* const* tensors, const int64_t* numels, int n, void* dst, size_t cap);
@@ -604,6 +605,38 @@ int rdn_physics_value(const int64_t* report, int nbins, double* out) {
   if (rc != RDN_OK) return rc;
   acc_rows_value(report, RDN_REPORT_ROWS(nbins), RDN_PHYS_ROW_WORDS, RDN_PHYS_QUANTITIES, 1, 1, true, out);
   return RDN_OK;
+  RDN_GUARD_END
+}
+
+// The arguments rdn_fir and rdn_median share (taps_ok: rdn_fir's taps pointer is given).
+static int check_filter_call(const std::string& fn, const float* x, const float* y, int64_t n, int64_t L, int w,
+                             bool taps_ok) {
+  if (!taps_ok || (n > 0 && !(x && y))) return fail(RDN_EINVAL, fn + ": null pointer");
+  if (n < 0) return fail(RDN_EINVAL, fn + ": need n >= 0");
+  if (w < 1 || w > RDN_FILTER_MAX_WINDOW || w % 2 == 0)
+    return fail(RDN_EINVAL, fn + ": the window must be odd, 1 <= w <= " + std::to_string(RDN_FILTER_MAX_WINDOW));
+  if (L < w || L > 0x7fffffff) return fail(RDN_EINVAL, fn + ": need w <= L < 2^31");
+  if (n > 0) {  // tiles re-read their neighbours' samples (the halo) while other tiles' outputs land in y
+    const uintptr_t xb = (uintptr_t)x, yb = (uintptr_t)y, bytes = (uintptr_t)n * (uintptr_t)L * sizeof(float);
+    if (xb < yb + bytes && yb < xb + bytes) return fail(RDN_EINVAL, fn + ": x and y overlap");
+  }
+  return RDN_OK;
+}
+
+int rdn_fir(const float* x, float* y, int64_t n, int64_t L, const double* taps, int w, const double* edge_taps,
+            void* stream) {
+  RDN_GUARD_BEGIN
+  const int rc = check_filter_call("rdn_fir", x, y, n, L, w, taps != nullptr);
+  if (rc != RDN_OK || n == 0) return rc;
+  return hip_check(rdn::launch_fir(x, y, n, (int)L, taps, w, edge_taps, (hipStream_t)stream), "fir");
+  RDN_GUARD_END
+}
+
+int rdn_median(const float* x, float* y, int64_t n, int64_t L, int w, void* stream) {
+  RDN_GUARD_BEGIN
+  const int rc = check_filter_call("rdn_median", x, y, n, L, w, true);
+  if (rc != RDN_OK || n == 0) return rc;
+  return hip_check(rdn::launch_median(x, y, n, (int)L, w, (hipStream_t)stream), "median");
   RDN_GUARD_END
 }
 

@@ -11,7 +11,7 @@
 // simulator's parameter bounds (rdn_generate with n = 0); and the
 // host side of the SNR report (rdn_snr's argument checks, rdn_report_bin, rdn_report_value on an
 // exactly-sized report) and of the PhysicsAwareLoss report (rdn_physics's argument checks,
-// rdn_physics_value).
+// rdn_physics_value); and the argument checks of the baseline filters (rdn_fir, rdn_median).
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -180,6 +180,38 @@ int main(int argc, char** argv) {
     EXPECT(t[0] == 3.0 && t[5] == 2.75 && t[6] == 3.0 && std::isnan(t[3]) && t[1] == 0.0);
     EXPECT(rdn_physics_value(rep.data(), 0, val.data()) == RDN_EINVAL);
     EXPECT(rdn_physics_value(nullptr, nb, val.data()) == RDN_EINVAL);
+  }
+
+  // baseline filters: every refusal comes before any HIP call, for n = 0 too
+  {
+    std::vector<float> buf(64, 0.f);
+    std::vector<double> tp(5, 0.2);
+    const float* x = buf.data();
+    float* y = buf.data() + 32;
+    EXPECT(rdn_fir(x, y, 1, 16, nullptr, 5, nullptr, nullptr) == RDN_EINVAL);             // null taps
+    EXPECT(rdn_fir(nullptr, nullptr, 0, 16, nullptr, 5, nullptr, nullptr) == RDN_EINVAL); // ... for n = 0 too
+    EXPECT(rdn_fir(nullptr, y, 1, 16, tp.data(), 5, nullptr, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_fir(x, nullptr, 1, 16, tp.data(), 5, nullptr, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_fir(x, y, -1, 16, tp.data(), 5, nullptr, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_fir(x, y, 1, 16, tp.data(), 4, nullptr, nullptr) == RDN_EINVAL);           // even
+    EXPECT(rdn_fir(x, y, 1, 16, tp.data(), 0, nullptr, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_fir(x, y, 1, 16, tp.data(), -3, nullptr, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_fir(x, y, 0, 1000, tp.data(), RDN_FILTER_MAX_WINDOW + 2, nullptr, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_fir(x, y, 1, 4, tp.data(), 5, nullptr, nullptr) == RDN_EINVAL);            // L < w
+    EXPECT(rdn_fir(x, y, 0, (int64_t)1 << 31, tp.data(), 5, nullptr, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_fir(x, buf.data() + 8, 1, 16, tp.data(), 5, nullptr, nullptr) == RDN_EINVAL);   // overlap
+    EXPECT(rdn_fir(nullptr, nullptr, 0, 16, tp.data(), 5, nullptr, nullptr) == RDN_OK);
+    EXPECT(rdn_fir(nullptr, nullptr, 0, ((int64_t)1 << 31) - 1, tp.data(), RDN_FILTER_MAX_WINDOW, nullptr, nullptr) == RDN_OK);
+    EXPECT(rdn_median(nullptr, y, 1, 16, 5, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_median(x, y, -1, 16, 5, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_median(x, y, 1, 16, 6, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_median(x, y, 0, 16, 0, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_median(x, y, 0, 1000, 257, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_median(x, y, 1, 4, 5, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_median(x, y, 0, (int64_t)1 << 31, 5, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_median(x, buf.data() + 15, 1, 16, 5, nullptr) == RDN_EINVAL);
+    EXPECT(rdn_median(nullptr, nullptr, 0, 16, 5, nullptr) == RDN_OK);
+    EXPECT(std::strlen(rdn_last_error()) > 0);
   }
 
   if (fails) return 1;

@@ -88,10 +88,10 @@ inline hipError_t with_clean(const void* clean, bool clean_f64, F f) {
 }
 
 // Walks a batch of n workgroups (one per spectrum) in launches of at most 2^31 - 1, the grid's limit in
-// x: launch(n0, nn) enqueues the nn of them that start at n0.
+// x: launch(n0, nn) enqueues the nn of them that start at n0.  (`chunk`: fewer spectra per launch, for a
+// kernel that runs several workgroups per spectrum.)
 template <class Launch>
-inline hipError_t launch_chunks(int64_t n, Launch launch) {
-  const int64_t chunk = 0x7fffffff;
+inline hipError_t launch_chunks(int64_t n, Launch launch, int64_t chunk = 0x7fffffff) {
   for (int64_t n0 = 0; n0 < n; n0 += chunk) launch(n0, n - n0 < chunk ? n - n0 : chunk);
   return hipGetLastError();
 }

@@ -9,16 +9,22 @@ Drop-in surfaces (reference file:line):
   PhysicsAwareLoss                                PIDN|APIDN/train.py loss class (physics.py: value on device; gradient eager,
                                                   or from the same launch with fused_backward=True: engine.physics_grad)
   evaluate(..., physics=), write_physics_report   the loss's terms over a test set, by SNR bin (engine.physics)
+  MovingAverage, SavitzkyGolay, GaussianSmooth,   the classical filters a result is compared with, on the device
+  MedianFilter, write_comparison                  (baselines.py, engine.fir / engine.median; no reference counterpart)
 """
 from . import engine
+from .baselines import (BASELINES, GaussianSmooth, MedianFilter, MovingAverage, SavitzkyGolay, gaussian_taps,
+                        savgol_taps)
 from ._lib import EngineError, RangeError
 from .dataset import load_dataset, save_dataset
 from .distributed import all_reduce_sums, shard
-from .evaluate import evaluate, write_metrics, write_physics_report, write_snr_report
+from .evaluate import evaluate, evaluate_synthetic, write_comparison, write_metrics, write_physics_report, write_snr_report
 from .models import ADSDN, APIDN, DSDN, MODELS, PIDN, DenoiseCNN, RRCDNet
 from .physics import PhysicsAwareLoss
 from .simulator import generate, generate_signals
 
 __all__ = ["engine", "DenoiseCNN", "RRCDNet", "DSDN", "ADSDN", "PIDN", "APIDN", "MODELS", "generate",
            "generate_signals", "evaluate", "write_metrics", "write_snr_report", "load_dataset", "save_dataset", "shard",
-           "all_reduce_sums", "EngineError", "RangeError", "PhysicsAwareLoss", "write_physics_report"]
+           "all_reduce_sums", "EngineError", "RangeError", "PhysicsAwareLoss", "write_physics_report", "evaluate_synthetic",
+           "write_comparison", "BASELINES", "MovingAverage", "SavitzkyGolay", "GaussianSmooth", "MedianFilter", "savgol_taps",
+           "gaussian_taps"]

@@ -53,6 +53,11 @@ def phys_words(nbins):
     return report_rows(nbins) * PHYS_ROW_WORDS
 
 
+# baseline filters (include/raman_mi355x.h RDN_FILTER_*)
+FILTER_MAX_WINDOW = 255
+FILTER_TILE = 2048
+
+
 def source_hash():
     """sha256 prefix of the sources the library is built from -- the same files, in the same order,
     as csrc/Makefile's STAMP_SRC (None when the sources are not beside the package)."""
@@ -125,6 +130,11 @@ _SIGNATURES = {
     "rdn_physics_grad": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                           ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
                           ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    # the classical baseline filters: likewise added to ABI v6 and detected by symbol
+    "rdn_fir": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
+                 ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rdn_median": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p],
+                   ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGNATURES)

@@ -684,3 +684,64 @@ def physics_grad(x, y, clean, weights=PHYS_WEIGHTS, scale=None, per_spectrum=Tru
                                            int(clean.dtype == torch.float64), n, L, alpha, beta, gamma, scale, _ptr(per),
                                            _ptr(grad), _stream(dev)), "rdn_physics_grad")
     return per, grad
+
+
+# ---- classical baseline filters (rdn_fir, rdn_median; the arithmetic contract: include/raman_mi355x.h) ----
+FILTER_TILE = _lib.FILTER_TILE                  # outputs per workgroup
+FILTER_MAX_WINDOW = _lib.FILTER_MAX_WINDOW
+
+
+def _filter_args(x, window, out):
+    """What fir() and median() do with x, the window and ``out`` before the launch: (x, y, n, L)."""
+    _check_cuda_f32(x, "input")
+    if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[1] != 1):
+        raise ValueError(f"expected (N, L) or (N, 1, L) input, got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError("input must be contiguous")
+    if isinstance(window, bool) or int(window) != window or not 1 <= int(window) <= FILTER_MAX_WINDOW or window % 2 == 0:
+        raise ValueError(f"the window must be an odd integer in [1, {FILTER_MAX_WINDOW}], got {window!r}")
+    n, L = x.shape[0], x.shape[-1]
+    if L < window:
+        raise ValueError(f"spectra of {L} samples are shorter than the window {window}")
+    y = torch.empty_like(x) if out is None else out
+    if out is not None:
+        _check_out(y, "out", x.shape, x.device)
+    if y.data_ptr() < x.data_ptr() + x.numel() * 4 and x.data_ptr() < y.data_ptr() + y.numel() * 4:
+        raise ValueError("out must not overlap the input (tiles re-read input halos while outputs are written)")
+    return x, y, n, L
+
+
+def _device_taps(t, name, shape, device):
+    """Filter coefficients as the kernel reads them: a contiguous float64 tensor of ``shape`` on ``device``
+    (a CUDA tensor is taken as it is; anything else is copied there)."""
+    if not (torch.is_tensor(t) and t.is_cuda):
+        t = torch.as_tensor(t, dtype=torch.float64).to(device)
+    _check_out(t, name, shape, device, torch.float64)
+    return t
+
+
+def fir(x, taps, edge_taps=None, out=None):
+    """FIR filter of every spectrum of ``x`` (float32 (N, L) or (N, 1, L), contiguous, CUDA) with the odd
+    number w = len(taps) of float64 ``taps``: y[i] = Σ_k taps[k] x[i - h + k], h = (w - 1) / 2, summed
+    sequentially in fp64 and rounded once to fp32 (rdn_fir).  The ends use mirror indexing (scipy's
+    mode='mirror'), or -- with ``edge_taps``, float64 (w - 1, w) -- the first and last h outputs are
+    row j of the table applied to the first / last w samples (savgol_filter's mode='interp').  Taps that
+    are not CUDA tensors are copied to the device on every call: a caller in a loop keeps them there.
+    ``out``: a float32 tensor of x's shape to write into (made when None); it must not overlap x."""
+    w = int(taps.shape[0]) if hasattr(taps, "shape") and len(taps.shape) == 1 else len(taps)
+    x, y, n, L = _filter_args(x, w, out)
+    taps = _device_taps(taps, "taps", (w,), x.device)
+    if edge_taps is not None:
+        edge_taps = _device_taps(edge_taps, "edge_taps", (w - 1, w), x.device)
+    _lib.check(_lib.lib().rdn_fir(_ptr(x), _ptr(y), n, L, _ptr(taps), w, _ptr(edge_taps), _stream(x.device)), "rdn_fir")
+    return y
+
+
+def median(x, window, out=None):
+    """Running median of every spectrum of ``x`` (float32 (N, L) or (N, 1, L), contiguous, CUDA) over the
+    odd ``window``, mirror indexing at the ends (scipy.ndimage.median_filter's mode='mirror'): each output
+    is bit for bit one of the inputs, ordered by the monotone key of their bits (-0 < +0); a window that
+    holds a NaN gives the quiet NaN (rdn_median).  ``out`` as in fir()."""
+    x, y, n, L = _filter_args(x, window, out)
+    _lib.check(_lib.lib().rdn_median(_ptr(x), _ptr(y), n, L, int(window), _stream(x.device)), "rdn_median")
+    return y

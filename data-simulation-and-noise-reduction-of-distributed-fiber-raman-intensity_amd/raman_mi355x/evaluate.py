@@ -157,6 +157,16 @@ def _finish(model, ws):
                               f"intensity); evaluate this data in 'fp32'")
 
 
+def _module_device(model):
+    """Where a module lives: its first parameter's device, else (a parameter-free baseline filter) its first
+    buffer's, else the current CUDA device."""
+    for t in model.parameters():
+        return t.device
+    for t in model.buffers():
+        return t.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
 def _workspace(model, n, L, device):
     if (not _engine_module(model) or not engine.needs_workspace(model.ARCH, model.engine_code)
             or torch.device(device).type != "cuda"):
@@ -226,7 +236,7 @@ def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bi
     ``snr_bins`` -- the same per bin of the key the SNR report bins by."""
     model.eval()
     if device is None:
-        device = next(model.parameters()).device
+        device = _module_device(model)
     device = torch.device(device)
     noisy = _as_rows(noisy_data)
     clean = _as_rows(clean_data)
@@ -272,7 +282,10 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
                        physics=None):
     """Config 4: ``total`` simulator spectra [first_index, first_index + total),
     sharded over the ranks as [r·N/W, (r+1)·N/W), each chunk generated on the device, denoised by
-    every model in ``models`` (name -> module) and metered into that model's exact accumulator.
+    every model in ``models`` (name -> module) and metered into that model's exact accumulator.  A module
+    that is not one of the engine's networks (a baseline filter of baselines.py, any ``nn.Module`` mapping
+    (N, 1, L) to (N, 1, L) on the device) runs its own forward and then the metrics kernel; it feeds the same
+    accumulator and reports, so its entry has a network's guarantees as far as its forward is deterministic.
     Returns {name: {"means", "spectra", "seconds", "spectra_per_s"}} with the all-reduced means
     (identical for any world size) and the max-over-ranks wall time of the loop.  ``log_every_s`` > 0
     prints progress to stderr about that often (the loop then waits for the device every 64 chunks,
@@ -303,7 +316,8 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
             model.eval()
             m = _Meters(device, snr_bins, weights)
             ws = _workspace(model, B, L, device)
-            packed = model.packed_weights(device)
+            eng = _engine_module(model)          # any other module (baselines.py) runs its own forward
+            packed = model.packed_weights(device) if eng else None
             if dist.is_available() and dist.is_initialized():
                 dist.barrier()
             torch.cuda.synchronize(device)
@@ -319,6 +333,11 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
                 nb = min(B, hi - b0)
                 _, _, snr_db, _ = engine.generate(nb, seed, first_index=first_index + b0, signal_length=L, device=device,
                                                   out=(clean[:nb], noisy[:nb]), **gen_kwargs)
+                if not eng:
+                    yb = model(noisy[:nb].view(nb, 1, L))
+                    per, _ = engine.metrics(yb.reshape(nb, L), clean[:nb], per_spectrum=m.per_spectrum, acc=m.acc)
+                    m.add(noisy[:nb], yb, clean[:nb], per, snr_db)
+                    continue
                 # forward + metric sums in one call: on the walk geometry the forward kernel meters each
                 # spectrum itself (no second pass over y); otherwise the metrics kernel follows it
                 if fused_metrics:
@@ -404,4 +423,31 @@ def write_physics_report(result, root):
             f.write(f"{k}: {part[k]:.6e}\n")
         if "by_snr" in part:
             _write_table(f, cols, [part["under"]] + list(part["by_snr"]) + [part["over"]], ".6e")
+    return root
+
+
+COMPARISON_KEYS = KEYS + SNR_KEYS
+
+
+def write_comparison(results, root):
+    """One line per model of an ``evaluate_synthetic`` result -- or of a dict name -> ``evaluate`` result --
+    into the directory ``root``: ``comparison.json`` (name -> its four means and, where the run had
+    ``snr_bins``, SNR_in, SNR_out and SNR_gain) and ``comparison.txt``, the same as a table ('-' where a run
+    had no SNR report).  Networks and baseline filters (baselines.py) evaluated by one call stand side by
+    side."""
+    import json
+    table = {}
+    for name, r in results.items():
+        means = r["means"] if "means" in r else r
+        row = {k: float(means[k]) for k in KEYS}
+        row.update({k: float(r[k]) for k in SNR_KEYS if k in r})
+        table[name] = row
+    os.makedirs(root, exist_ok=True)
+    with open(os.path.join(root, "comparison.json"), "w") as f:
+        json.dump(table, f, indent=1)
+    with open(os.path.join(root, "comparison.txt"), "w") as f:
+        f.write("model " + " ".join(COMPARISON_KEYS) + "\n")
+        for name, row in table.items():
+            f.write(name + " " + " ".join(format(row[k], ".6e" if k in KEYS else ".4f") if k in row else "-"
+                                          for k in COMPARISON_KEYS) + "\n")
     return root

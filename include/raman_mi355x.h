@@ -406,6 +406,42 @@ int rdn_physics_grad(const float* x, const float* y, const void* clean, int clea
  * quantity with an out-of-range value in that row (the contract of rdn_acc_value). */
 int rdn_physics_value(const int64_t* report, int nbins, double* out);
 
+/* ---- classical baseline filters (added to ABI v6 without a version bump: detect by symbol) ----
+ *
+ * The filters a denoising result is compared with -- moving average, Gaussian, Savitzky-Golay (rdn_fir) and
+ * the running median (rdn_median) -- on device-resident spectra, so that their columns of a comparison come
+ * from the same meters as a network's.  x, y: fp32 [n][L] device, y WRITTEN; w: the odd window,
+ * 1 <= w <= RDN_FILTER_MAX_WINDOW, h = (w - 1) / 2.  A spectrum's output bits depend on its own samples
+ * only: not on n, its row index or the launches a huge n is split into.
+ *
+ * Mirror indexing (scipy's mode='mirror', no repeated edge sample): idx(j) = -j for j < 0,
+ * 2 (L - 1) - j for j > L - 1, j otherwise.
+ *
+ * rdn_fir, taps: fp64 [w] DEVICE.  In fp64, products and sums each rounded on their own, in this order,
+ * never fused:
+ *   acc = 0.0;  for k = 0 .. w-1:  acc = acc + taps[k] * (double)x[idx(i - h + k)];   y[i] = (float)acc
+ * (one final rounding to fp32; fp32 subnormals are read as their values).  edge_taps: NULL, or fp64
+ * [w - 1][w] DEVICE: the first and last h outputs then run the same recurrence over a fixed window,
+ *   y[j]         = sum_k edge_taps[j][k]     * x[k]           j < h
+ *   y[L - h + j] = sum_k edge_taps[h + j][k] * x[L - w + k]   j < h
+ * which is how scipy's savgol_filter(mode='interp') is expressed.  Non-finite inputs or taps give the
+ * IEEE result of the recurrence.
+ *
+ * rdn_median: samples are ordered by the monotone unsigned key of their fp32 bits (bits ^ 0x80000000 for a
+ * clear sign bit, ~bits for a set one: -0 < +0, and -inf and +inf are ordinary values).  y[i] is the sample
+ * of rank h among x[idx(i - h)] .. x[idx(i + h)], bit for bit one of the inputs; a window that holds a NaN
+ * gives the quiet NaN 0x7fc00000.
+ *
+ * RDN_EINVAL, checked before any device call and also for n = 0: a NULL taps; n < 0; w even, w < 1 or
+ * w > RDN_FILTER_MAX_WINDOW; L < w or L >= 2^31; for n > 0 a NULL x or y, or x and y overlapping.  n = 0
+ * launches nothing and accepts NULL data pointers.  taps and edge_taps stay the caller's: the library keeps
+ * no device state and never synchronises; the call is asynchronous on `stream`. */
+#define RDN_FILTER_MAX_WINDOW 255
+#define RDN_FILTER_TILE 2048         /* outputs per workgroup (tests probe the sizes around it) */
+int rdn_fir(const float* x, float* y, int64_t n, int64_t L, const double* taps, int w,
+            const double* edge_taps /* device [w-1][w] or NULL = mirror */, void* stream);
+int rdn_median(const float* x, float* y, int64_t n, int64_t L, int w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

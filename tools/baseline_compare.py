@@ -1,0 +1,97 @@
+"""The networks beside the classical filters, from one evaluate_synthetic call, and each filter's throughput
+(DESIGN.md §5).
+
+Part 1 meters the six trained-fixture networks (tests/golden, 'trained' weights, 'f16') and a small grid of
+baseline filters over the same on-device simulator spectra with snr_bins = (20, 37, 17), and writes the table
+to profiles/baselines/comparison.json / comparison.txt (raman_mi355x.write_comparison).
+
+Part 2 times each filter alone at L = 10 000, batch 8192, with HIP events on the launch stream, the filters
+interleaved round by round (round 0 warms up), and writes spectra/s and GB/s (80 KB of HBM traffic per
+spectrum: 40 KB read, 40 KB written) beside the HBM-bound time into profiles/baselines/throughput.json.
+
+    python tools/baseline_compare.py [--total 8192] [--L 10000] [--batch 2048] [--rounds 12] [--out profiles/baselines]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "data-simulation-and-noise-reduction-of-distributed-fiber-raman-intensity_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, ROOT)
+
+HBM_ACHIEVABLE = 6.29e12          # bytes/s, float4 copy on the MI355X (8.0e12 spec)
+BYTES_PER_SAMPLE = 8              # one fp32 read, one fp32 written
+
+
+def baseline_grid():
+    from raman_mi355x import baselines as B
+    return {"ma3": B.MovingAverage(3), "ma5": B.MovingAverage(5), "sg5_2": B.SavitzkyGolay(5, 2),
+            "sg21_3": B.SavitzkyGolay(21, 3), "gauss1": B.GaussianSmooth(1.0), "gauss2.5": B.GaussianSmooth(2.5),
+            "med3": B.MedianFilter(3), "med5": B.MedianFilter(5), "med7": B.MedianFilter(7), "med21": B.MedianFilter(21)}
+
+
+def main():
+    import torch
+    import raman_mi355x as R
+    from conftest import golden_state_dict
+    from raman_mi355x import engine
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--total", type=int, default=8192)
+    ap.add_argument("--L", type=int, default=10000)
+    ap.add_argument("--batch", type=int, default=2048)
+    ap.add_argument("--time-batch", type=int, default=8192)
+    ap.add_argument("--rounds", type=int, default=12)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "baselines"))
+    a = ap.parse_args()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    filters = {k: m.to(dev) for k, m in baseline_grid().items()}
+
+    models = {}
+    for arch in R.MODELS:
+        m = R.MODELS[arch]()
+        m.load_state_dict(golden_state_dict(arch, "trained"), strict=True)
+        models[arch] = m.to(dev).eval().set_engine_dtype("f16")
+    models.update(filters)
+    res = R.evaluate_synthetic(models, a.total, signal_length=a.L, batch_size=a.batch, device=dev, snr_bins=(20, 37, 17))
+    R.write_comparison(res, a.out)
+    print(open(os.path.join(a.out, "comparison.txt")).read(), flush=True)
+
+    n, L = a.time_batch, a.L
+    _, noisy, _, _ = engine.generate(n, 1, signal_length=L, device=dev)
+    x = noisy.view(n, 1, L)
+    y = torch.empty_like(x)
+    legs = {k: ((lambda m=m: engine.median(x, m.window, out=y)) if isinstance(m, R.MedianFilter) else
+                (lambda m=m: engine.fir(x, m.taps, edge_taps=m.edge_taps, out=y))) for k, m in filters.items()}
+    for w in (11, 25, 27, 101):                                         # sorting networks up to 25, then the radix select
+        legs[f"med{w}"] = lambda w=w: engine.median(x, w, out=y)
+    legs["sg255_3"] = (lambda m=R.SavitzkyGolay(255, 3).to(dev): engine.fir(x, m.taps, edge_taps=m.edge_taps, out=y))
+    legs["copy"] = lambda: y.copy_(x)                                   # the HBM-bound yardstick, measured
+    times = {k: [] for k in legs}
+    for rnd in range(a.rounds + 1):
+        for name, leg in legs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            leg()
+            e1.record()
+            torch.cuda.synchronize()
+            if rnd:
+                times[name].append(e0.elapsed_time(e1))
+    nbytes = n * L * BYTES_PER_SAMPLE
+    bound_ms = nbytes / HBM_ACHIEVABLE * 1e3
+    table = {"batch": n, "L": L, "rounds": a.rounds, "bytes": nbytes, "hbm_bound_ms": bound_ms, "filters": {}}
+    print(f"B={n} L={L}: {nbytes / 1e6:.1f} MB per call, HBM-bound {bound_ms:.3f} ms at {HBM_ACHIEVABLE / 1e12:.2f} TB/s")
+    for name, t in times.items():
+        med = statistics.median(t)
+        table["filters"][name] = {"median_ms": med, "min_ms": min(t), "max_ms": max(t), "spectra_per_s": n / med * 1e3,
+                                  "GB_per_s": nbytes / med / 1e6, "times_hbm_bound": med / bound_ms}
+        print(f"{name:9s} median {med:9.3f} ms  min {min(t):9.3f}  max {max(t):9.3f}  {n / med * 1e3:12.0f} spectra/s  "
+              f"{nbytes / med / 1e6:8.1f} GB/s  {med / bound_ms:7.1f} x HBM-bound", flush=True)
+    with open(os.path.join(a.out, "throughput.json"), "w") as f:
+        json.dump(table, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
