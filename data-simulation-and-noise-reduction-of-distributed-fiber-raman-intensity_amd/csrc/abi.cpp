@@ -14,6 +14,7 @@
 #include "snr.hpp"
 #include "physics.hpp"
 #include "filters.hpp"
+#include "haar.hpp"
 
 namespace rdn {
 std::string pack(int arch, int dtype, const float* const* tensors, const int64_t* numels, int n, void* dst, size_t cap);
@@ -637,6 +638,34 @@ int rdn_median(const float* x, float* y, int64_t n, int64_t L, int w, void* stre
   const int rc = check_filter_call("rdn_median", x, y, n, L, w, true);
   if (rc != RDN_OK || n == 0) return rc;
   return hip_check(rdn::launch_median(x, y, n, (int)L, w, (hipStream_t)stream), "median");
+  RDN_GUARD_END
+}
+
+int rdn_haar_shrink(const float* x, float* y, double* med, int64_t n, int64_t L, int levels, const double* k, int mode,
+                    void* stream) {
+  RDN_GUARD_BEGIN
+  const std::string fn = "rdn_haar_shrink";
+  if (!k || (n > 0 && !(x && y && med))) return fail(RDN_EINVAL, fn + ": null pointer");
+  if (n < 0) return fail(RDN_EINVAL, fn + ": need n >= 0");
+  if (levels < 1 || levels > RDN_HAAR_MAX_LEVELS)
+    return fail(RDN_EINVAL, fn + ": need 1 <= levels <= " + std::to_string(RDN_HAAR_MAX_LEVELS));
+  if (mode != RDN_HAAR_SOFT && mode != RDN_HAAR_HARD) return fail(RDN_EINVAL, fn + ": unknown mode " + std::to_string(mode));
+  if (L < ((int64_t)1 << levels) || L > 0x7fffffff) return fail(RDN_EINVAL, fn + ": need 2^levels <= L < 2^31");
+  rdn::haar::Factors f = {};
+  for (int j = 0; j < levels; ++j) {
+    if (!std::isfinite(k[j]) || k[j] < 0.0) return fail(RDN_EINVAL, fn + ": every k must be finite and >= 0");
+    f.k[j] = k[j];
+  }
+  if (n > 0) {  // tiles re-read their neighbours' samples (the halo) while other tiles' outputs land in y
+    const uintptr_t xb = (uintptr_t)x, yb = (uintptr_t)y, bytes = (uintptr_t)n * (uintptr_t)L * sizeof(float);
+    if (xb < yb + bytes && yb < xb + bytes) return fail(RDN_EINVAL, fn + ": x and y overlap");
+    // med is written by the select kernel while x is still to be read, and read while y is written
+    const uintptr_t mb = (uintptr_t)med, mbytes = (uintptr_t)n * sizeof(double);
+    if ((mb < xb + bytes && xb < mb + mbytes) || (mb < yb + bytes && yb < mb + mbytes))
+      return fail(RDN_EINVAL, fn + ": med overlaps x or y");
+  }
+  if (n == 0) return RDN_OK;
+  return hip_check(rdn::launch_haar_shrink(x, y, med, n, (int)L, levels, f, mode, (hipStream_t)stream), "haar_shrink");
   RDN_GUARD_END
 }
 

@@ -11,6 +11,8 @@ Drop-in surfaces (reference file:line):
   evaluate(..., physics=), write_physics_report   the loss's terms over a test set, by SNR bin (engine.physics)
   MovingAverage, SavitzkyGolay, GaussianSmooth,   the classical filters a result is compared with, on the device
   MedianFilter, write_comparison                  (baselines.py, engine.fir / engine.median; no reference counterpart)
+  HaarShrink, haar_thresholds                     translation-invariant Haar wavelet shrinkage with a blind per-spectrum
+                                                  noise estimate (wavelets.py, engine.haar_shrink; no reference counterpart)
 """
 from . import engine
 from .baselines import (BASELINES, GaussianSmooth, MedianFilter, MovingAverage, SavitzkyGolay, gaussian_taps,
@@ -22,9 +24,10 @@ from .evaluate import evaluate, evaluate_synthetic, write_comparison, write_metr
 from .models import ADSDN, APIDN, DSDN, MODELS, PIDN, DenoiseCNN, RRCDNet
 from .physics import PhysicsAwareLoss
 from .simulator import generate, generate_signals
+from .wavelets import HaarShrink, haar_thresholds
 
 __all__ = ["engine", "DenoiseCNN", "RRCDNet", "DSDN", "ADSDN", "PIDN", "APIDN", "MODELS", "generate",
            "generate_signals", "evaluate", "write_metrics", "write_snr_report", "load_dataset", "save_dataset", "shard",
            "all_reduce_sums", "EngineError", "RangeError", "PhysicsAwareLoss", "write_physics_report", "evaluate_synthetic",
            "write_comparison", "BASELINES", "MovingAverage", "SavitzkyGolay", "GaussianSmooth", "MedianFilter", "savgol_taps",
-           "gaussian_taps"]
+           "gaussian_taps", "HaarShrink", "haar_thresholds"]

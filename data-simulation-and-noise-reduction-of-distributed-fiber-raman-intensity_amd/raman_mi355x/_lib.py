@@ -56,6 +56,11 @@ def phys_words(nbins):
 # baseline filters (include/raman_mi355x.h RDN_FILTER_*)
 FILTER_MAX_WINDOW = 255
 FILTER_TILE = 2048
+# translation-invariant Haar shrinkage (include/raman_mi355x.h RDN_HAAR_*)
+HAAR_MAX_LEVELS = 7
+HAAR_TILE = 512
+HAAR_SELECT_LDS_L = 12288
+HAAR_SOFT, HAAR_HARD = 0, 1
 
 
 def source_hash():
@@ -135,6 +140,9 @@ _SIGNATURES = {
                  ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
     "rdn_median": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p],
                    ctypes.c_int),
+    # translation-invariant Haar shrinkage: likewise added to ABI v6 and detected by symbol
+    "rdn_haar_shrink": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                         c_double_p, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGNATURES)

@@ -745,3 +745,50 @@ def median(x, window, out=None):
     x, y, n, L = _filter_args(x, window, out)
     _lib.check(_lib.lib().rdn_median(_ptr(x), _ptr(y), n, L, int(window), _stream(x.device)), "rdn_median")
     return y
+
+
+# ---- translation-invariant Haar shrinkage (rdn_haar_shrink; the arithmetic contract: include/raman_mi355x.h) ----
+HAAR_TILE = _lib.HAAR_TILE                      # outputs per workgroup
+HAAR_MAX_LEVELS = _lib.HAAR_MAX_LEVELS
+HAAR_SELECT_LDS_L = _lib.HAAR_SELECT_LDS_L      # longer spectra: the median's select passes re-read them through L2
+HAAR_MODES = {"soft": _lib.HAAR_SOFT, "hard": _lib.HAAR_HARD}
+
+
+def haar_shrink(x, k, mode="hard", out=None, med=None):
+    """Translation-invariant Haar shrinkage of every spectrum of ``x`` (float32 (N, L) or (N, 1, L), contiguous,
+    CUDA) over J = len(k) levels, 1 <= J <= 7, 2^J <= L: the undecimated Haar transform with periodic indexing,
+    detail plane j thresholded (``mode`` 'hard' or 'soft') at k[j - 1] * m, m the spectrum's median |d_1|, and
+    the inverse transform, all in fp64 and rounded once to fp32 (rdn_haar_shrink).  ``k``: J host floats, finite
+    and >= 0 (wavelets.haar_thresholds).  Returns (y, med): y float32 of x's shape, med float64 (N,), m per
+    spectrum; a spectrum with a NaN or an infinity gives NaN in both.  ``out`` / ``med``: buffers to write into
+    (made when None); out must not overlap x, and med neither of them."""
+    _check_cuda_f32(x, "input")
+    if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[1] != 1):
+        raise ValueError(f"expected (N, L) or (N, 1, L) input, got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError("input must be contiguous")
+    if mode not in HAAR_MODES:
+        raise ValueError(f"mode must be 'soft' or 'hard', got {mode!r}")
+    k = [float(v) for v in (k.tolist() if hasattr(k, "tolist") else k)]
+    J = len(k)
+    if not 1 <= J <= HAAR_MAX_LEVELS:
+        raise ValueError(f"need 1 to {HAAR_MAX_LEVELS} levels, got {J} thresholds")
+    if not all(0.0 <= v < float("inf") for v in k):
+        raise ValueError(f"every threshold factor must be finite and >= 0, got {k}")
+    n, L = x.shape[0], x.shape[-1]
+    if L < 2 ** J:
+        raise ValueError(f"spectra of {L} samples are shorter than 2^{J}, the reach of {J} levels")
+    y = torch.empty_like(x) if out is None else out
+    if out is not None:
+        _check_out(y, "out", x.shape, x.device)
+    if y.data_ptr() < x.data_ptr() + x.numel() * 4 and x.data_ptr() < y.data_ptr() + y.numel() * 4:
+        raise ValueError("out must not overlap the input (tiles re-read input halos while outputs are written)")
+    m = torch.empty(n, dtype=torch.float64, device=x.device) if med is None else med
+    if med is not None:
+        _check_out(m, "med", (n,), x.device, torch.float64)
+        for t, name in ((x, "the input"), (y, "out")):
+            if m.data_ptr() < t.data_ptr() + t.numel() * 4 and t.data_ptr() < m.data_ptr() + m.numel() * 8:
+                raise ValueError(f"med must not overlap {name}")
+    _lib.check(_lib.lib().rdn_haar_shrink(_ptr(x), _ptr(y), _ptr(m), n, L, J, (ctypes.c_double * J)(*k), HAAR_MODES[mode],
+                                          _stream(x.device)), "rdn_haar_shrink")
+    return y, m

@@ -442,6 +442,46 @@ int rdn_fir(const float* x, float* y, int64_t n, int64_t L, const double* taps, 
             const double* edge_taps /* device [w-1][w] or NULL = mirror */, void* stream);
 int rdn_median(const float* x, float* y, int64_t n, int64_t L, int w, void* stream);
 
+/* ---- translation-invariant Haar shrinkage (added to ABI v6 without a version bump: detect by symbol) ----
+ *
+ * The classical denoiser of a piecewise-constant signal under white noise: the undecimated (a trous) Haar
+ * transform of each spectrum, its detail planes thresholded in units of the spectrum's own noise estimate,
+ * and the inverse transform (Coifman & Donoho's cycle spinning).  x, y: fp32 [n][L] device, y WRITTEN;
+ * J = levels, 1 <= J <= RDN_HAAR_MAX_LEVELS, 2^J <= L < 2^31; k: fp64 [J] HOST, each finite and >= 0.
+ * Indexing is periodic: idx(j) = j mod L, taken non-negative.  All arithmetic is fp64, each operation rounded
+ * on its own, none fused:
+ *   a_0[i] = (double)x[i]
+ *   for j = 1..J, s = 2^(j-1):   p = a_{j-1}[i],  q = a_{j-1}[idx(i - s)]
+ *       a_j[i] = 0.5 * (p + q)        d_j[i] = 0.5 * (p - q)
+ *   m = median over i in [0, L) of |d_1[i]|   (numpy's: rank (L-1)/2 for odd L; 0.5 * (lo + hi) of ranks
+ *                                              L/2-1, L/2 for even L)
+ *   t_j = k[j-1] * m                                  (one product)
+ *   RDN_HAAR_SOFT:  e_j = d_j - t_j if d_j > t_j;  d_j + t_j if d_j < -t_j;  else +0.0
+ *   RDN_HAAR_HARD:  e_j = d_j if |d_j| > t_j;  else +0.0
+ *   b_J = a_J;  for j = J..1, s = 2^(j-1):
+ *       b_{j-1}[i] = 0.5 * ((b_j[i] + e_j[i]) + (b_j[idx(i + s)] - e_j[idx(i + s)]))
+ *   y[i] = (float)b_0[i]                              (one rounding to fp32)
+ * med: fp64 [n] device, WRITTEN: m of each spectrum.  A spectrum that holds a NaN or an infinity gives the
+ * quiet NaN 0x7fc00000 at every output and NaN in med.  fp32 subnormals are read as their values.  A
+ * spectrum's output bits depend on its own samples only: not on n, its row index, the tiling or the launches
+ * a huge n is split into.
+ *
+ * With every k = 0 this is a perfect-reconstruction transform.  With
+ * k[j-1] = lambda * 2^((1-j)/2) / 0.6744897501960817 it is cycle spinning over all 2^J shifts of the
+ * orthonormal decimated Haar transform with threshold lambda * sigma, where
+ * sigma = m * sqrt(2) / 0.6744897501960817 is the MAD estimate of the noise.
+ *
+ * RDN_EINVAL, checked before any device call and also for n = 0: a NULL k; a k entry that is negative or not
+ * finite; levels outside [1, RDN_HAAR_MAX_LEVELS]; an unknown mode; L < 2^levels or L >= 2^31; n < 0; for
+ * n > 0 a NULL x, y or med, x and y overlapping, or med overlapping x or y.  n = 0 launches nothing.  The library keeps no device
+ * state and never synchronises; med is the caller's buffer; the call is asynchronous on `stream`. */
+#define RDN_HAAR_MAX_LEVELS 7
+#define RDN_HAAR_TILE 512            /* outputs per workgroup (tests probe the sizes around it) */
+#define RDN_HAAR_SELECT_LDS_L 12288  /* longer spectra are re-read through L2 by the median's select passes */
+enum { RDN_HAAR_SOFT = 0, RDN_HAAR_HARD = 1 };
+int rdn_haar_shrink(const float* x, float* y, double* med, int64_t n, int64_t L, int levels,
+                    const double* k /* HOST [levels] */, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 (DESIGN.md §5).
 
 Part 1 meters the six trained-fixture networks (tests/golden, 'trained' weights, 'f16') and a small grid of
-baseline filters over the same on-device simulator spectra with snr_bins = (20, 37, 17), and writes the table
+baseline filters (linear smoothers, running medians, translation-invariant Haar shrinkage) over the same
+on-device simulator spectra with snr_bins = (20, 37, 17), and writes the table
 to profiles/baselines/comparison.json / comparison.txt (raman_mi355x.write_comparison).
 
 Part 2 times each filter alone at L = 10 000, batch 8192, with HIP events on the launch stream, the filters
@@ -28,7 +29,9 @@ BYTES_PER_SAMPLE = 8              # one fp32 read, one fp32 written
 
 def baseline_grid():
     from raman_mi355x import baselines as B
-    return {"ma3": B.MovingAverage(3), "ma5": B.MovingAverage(5), "sg5_2": B.SavitzkyGolay(5, 2),
+    from raman_mi355x.wavelets import HaarShrink
+    return {"haar4_3h": HaarShrink(), "haar3_1.5s": HaarShrink(3, 1.5, "soft"), "haar4_uni_h": HaarShrink(4, "universal"),
+            "ma3": B.MovingAverage(3), "ma5": B.MovingAverage(5), "sg5_2": B.SavitzkyGolay(5, 2),
             "sg21_3": B.SavitzkyGolay(21, 3), "gauss1": B.GaussianSmooth(1.0), "gauss2.5": B.GaussianSmooth(2.5),
             "med3": B.MedianFilter(3), "med5": B.MedianFilter(5), "med7": B.MedianFilter(7), "med21": B.MedianFilter(21)}
 
@@ -63,8 +66,11 @@ def main():
     _, noisy, _, _ = engine.generate(n, 1, signal_length=L, device=dev)
     x = noisy.view(n, 1, L)
     y = torch.empty_like(x)
+    med_buf = torch.empty(n, dtype=torch.float64, device=dev)
     legs = {k: ((lambda m=m: engine.median(x, m.window, out=y)) if isinstance(m, R.MedianFilter) else
+                (lambda m=m: engine.haar_shrink(x, m.factors(L), m.mode, out=y, med=med_buf)) if isinstance(m, R.HaarShrink) else
                 (lambda m=m: engine.fir(x, m.taps, edge_taps=m.edge_taps, out=y))) for k, m in filters.items()}
+    legs["haar7_3h"] = lambda m=R.HaarShrink(7): engine.haar_shrink(x, m.factors(L), m.mode, out=y, med=med_buf)
     for w in (11, 25, 27, 101):                                         # sorting networks up to 25, then the radix select
         legs[f"med{w}"] = lambda w=w: engine.median(x, w, out=y)
     legs["sg255_3"] = (lambda m=R.SavitzkyGolay(255, 3).to(dev): engine.fir(x, m.taps, edge_taps=m.edge_taps, out=y))
@@ -87,7 +93,7 @@ def main():
         med = statistics.median(t)
         table["filters"][name] = {"median_ms": med, "min_ms": min(t), "max_ms": max(t), "spectra_per_s": n / med * 1e3,
                                   "GB_per_s": nbytes / med / 1e6, "times_hbm_bound": med / bound_ms}
-        print(f"{name:9s} median {med:9.3f} ms  min {min(t):9.3f}  max {max(t):9.3f}  {n / med * 1e3:12.0f} spectra/s  "
+        print(f"{name:11s} median {med:9.3f} ms  min {min(t):9.3f}  max {max(t):9.3f}  {n / med * 1e3:12.0f} spectra/s  "
               f"{nbytes / med / 1e6:8.1f} GB/s  {med / bound_ms:7.1f} x HBM-bound", flush=True)
     with open(os.path.join(a.out, "throughput.json"), "w") as f:
         json.dump(table, f, indent=1)
