@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include "netspec.hpp"
 #include "host_util.hpp"
+#include "geometry.hpp"
 #include "snr.hpp"
 #include "physics.hpp"
 #include "filters.hpp"
@@ -70,6 +71,10 @@ int hip_check(hipError_t e, const char* what) {
 
 bool valid_arch(int a) { return a >= RDN_DENOISECNN && a <= RDN_APIDN; }
 bool valid_dtype(int d) { return d >= RDN_F32 && d <= RDN_F16MIX; }
+// a batch of n rows of L samples, lo <= L: not (n >= 0 and lo <= L < 2^31)
+bool bad_rows(int64_t n, int64_t L, int64_t lo) { return n < 0 || L < lo || L > 0x7fffffff; }
+// bytes of n (>= 0) float32 rows of L samples; 0 for an empty batch, which overlaps nothing
+size_t row_bytes(int64_t n, int64_t L) { return (size_t)n * (size_t)L * sizeof(float); }
 bool is_cbam(int a) { return a == RDN_ADSDN || a == RDN_APIDN; }
 // the dtypes whose e4m3 correction planes bound the activations (RDN_ERANGE, inplace.hpp range_vote)
 bool range_checked(int d) { return d == RDN_F16F8 || d == RDN_F16MIX; }
@@ -207,7 +212,7 @@ int rdn_workspace_size(int arch, int dtype, int64_t n, int64_t L, size_t* bytes,
 
 int rdn_workspace_init(int arch, int dtype, int64_t n, int64_t L, void* ws, size_t ws_bytes, void* stream) {
   RDN_GUARD_BEGIN
-  if (!valid_arch(arch) || !valid_dtype(dtype) || n < 0 || L < 1 || L > 0x7fffffff)
+  if (!valid_arch(arch) || !valid_dtype(dtype) || bad_rows(n, L, 1))
     return fail(RDN_EINVAL, "rdn_workspace_init: bad argument");
   if (unsupported(arch, dtype)) return fail_unsupported("rdn_workspace_init");
   const hipStream_t s = (hipStream_t)stream;
@@ -224,36 +229,10 @@ int rdn_workspace_init(int arch, int dtype, int64_t n, int64_t L, void* ws, size
   RDN_GUARD_END
 }
 
-// Latency geometry: a launch whose 640-row tiles would occupy at most half the CUs (the reference's
-// evaulate.py calls the model one spectrum at a time: 18 workgroups at L = 10,000) runs RDN_F16 /
-// RDN_F16MIX on 256-row tiles instead (2.8x the workgroups, each layer ~0.4x as long).  RDN_SHORT_TILES
-// = 0 / 1 forces either geometry (tests compare the two).
-static bool short_tiles(int arch, int64_t n, int64_t L, hipStream_t s) {
-  const char* env = std::getenv("RDN_SHORT_TILES");
-  if (env && (env[0] == '0' || env[0] == '1')) return env[0] == '1';
-  const int64_t T = rdn::H16_WB - 2 * rdn::fused_halo(arch), tiles = (L + T - 1) / T;
-  const int cus = rdn::device_cus(rdn::stream_device(s));
-  return cus > 0 && 2 * n * tiles <= cus;
-}
-
-// Walk geometry (one workgroup walks a whole spectrum, no halo recompute: fused16_walk.hip for RDN_F16
-// on DenoiseCNN / RRCDNet / DSDN / PIDN -- the networks with a walk_shift -- in 576-row tiles;
-// rrcdnet_hybrid_walk.hpp for RDN_F16MIX RRCDNet, 576-row tiles, RDN_WALK_ROWS_MIX) when
-// its predicted time -- rounds of the CUs x tiles per spectrum x rows per tile -- is below that of the
-// 640-row tiles (rounds x 640 rows): large batches.  RDN_WALK = 0 / 1 forces either geometry (tests
-// compare the two).
-static bool walk_tiles(int arch, int dtype, int64_t n, int64_t L, hipStream_t s) {
-  if (!rdn::walk_shift(arch) || (dtype != RDN_F16 && dtype != RDN_F16MIX)) return false;
-  const int64_t rows = dtype == RDN_F16MIX ? RDN_WALK_ROWS_MIX : rdn::H16_WALK_ROWS;
-  const char* env = std::getenv("RDN_WALK");
-  if (env && (env[0] == '0' || env[0] == '1')) return env[0] == '1';
-  const int64_t cus = rdn::device_cus(rdn::stream_device(s));
-  if (cus <= 0) return false;
-  const int64_t T = rdn::H16_WB - 2 * rdn::fused_halo(arch), tiles = (L + T - 1) / T;
-  const int64_t wt = (L + rdn::walk_shift(arch) + rows - 1) / rows;
-  const int64_t walk_rows = (n + cus - 1) / cus * wt * rows;
-  const int64_t tile_rows = (n * tiles + cus - 1) / cus * rdn::H16_WB;
-  return walk_rows < tile_rows;
+// RDN_SHORT_TILES / RDN_WALK = 0 / 1 force either answer of forward_geometry (geometry.hpp); -1: not set
+static int env_override(const char* name) {
+  const char* env = std::getenv(name);
+  return env && (env[0] == '0' || env[0] == '1') ? env[0] - '0' : -1;
 }
 
 // The forward of rdn_forward / rdn_forward_metrics.  mo (may be NULL): metrics of y against mo->clean;
@@ -264,13 +243,11 @@ static int forward_impl(const char* who, int arch, int dtype, const void* packed
   if (!valid_arch(arch) || !valid_dtype(dtype)) return fail(RDN_EINVAL, std::string(who) + ": unknown arch/dtype");
   // x / y may be NULL for an empty batch (an empty torch tensor's data pointer); the blob may not
   if (!packed || (n > 0 && (!x || !y))) return fail(RDN_EINVAL, std::string(who) + ": null pointer");
-  if (n < 0 || L < 1 || L > 0x7fffffff) return fail(RDN_EINVAL, std::string(who) + ": need n >= 0 and 1 <= L < 2^31");
+  if (bad_rows(n, L, 1)) return fail(RDN_EINVAL, std::string(who) + ": need n >= 0 and 1 <= L < 2^31");
   if (mo && L < 7) return fail(RDN_EINVAL, std::string(who) + ": need L >= 7 (SSIM window)");
   if (n == 0) return RDN_OK;
-  {  // tiles re-read their input halos while other tiles' outputs (and parked head rows) land in y
-    const uintptr_t xb = (uintptr_t)x, yb = (uintptr_t)y, bytes = (uintptr_t)(n * L) * sizeof(float);
-    if (xb < yb + bytes && yb < xb + bytes) return fail(RDN_EINVAL, std::string(who) + ": x and y overlap");
-  }
+  // tiles re-read their input halos while other tiles' outputs (and parked head rows) land in y
+  if (rdn::overlaps(x, row_bytes(n, L), y, row_bytes(n, L))) return fail(RDN_EINVAL, std::string(who) + ": x and y overlap");
   if (unsupported(arch, dtype)) return fail_unsupported(who);
   const uint8_t* blob = (const uint8_t*)packed;
   hipError_t e = hipSuccess;
@@ -284,19 +261,26 @@ static int forward_impl(const char* who, int arch, int dtype, const void* packed
     // status word of the 16-bit dtypes (optional: without a workspace a saturated tile still writes NaN,
     // and the input gate is not reported)
     unsigned* status = status_word(dtype) && ws && ws_bytes >= RANGE_WS_BYTES ? (unsigned*)ws : nullptr;
-    const bool shrt = dtype != RDN_BF16 && short_tiles(arch, n, L, s);
-    const bool walk = dtype != RDN_BF16 && !shrt && walk_tiles(arch, dtype, n, L, s);
     // the epilogue's direct path (spectra too long for the LDS, metrics.hpp walk_metrics_t) addresses y
     // with 32-bit byte counts: from L = 2^29 on the walk runs without it (kmo) and the metrics kernel follows
     const rdn::met::MetricOut* kmo = L < ((int64_t)1 << 29) ? mo : nullptr;
-    if (dtype == RDN_BF16) e = rdn::launch_fused16(arch, blob, x, y, n, (int)L, status, s);
-    else if (dtype == RDN_F16 && walk) e = rdn::launch_fused16_f16_walk(arch, blob, x, y, n, (int)L, status, kmo, s), done = kmo != nullptr;
-    else if (dtype == RDN_F16)
-      e = shrt ? rdn::launch_fused16_f16_small(arch, blob, x, y, n, (int)L, status, s)
-               : rdn::launch_fused16_f16(arch, blob, x, y, n, (int)L, status, s);
-    else if (dtype == RDN_F16MIX && walk) e = rdn::launch_fused_inplace_walk(blob, x, y, n, (int)L, status, kmo, s), done = kmo != nullptr;
-    else if (dtype == RDN_F16MIX && shrt) e = rdn::launch_fused_inplace_short(blob, x, y, n, (int)L, status, s);
-    else e = rdn::launch_fused_inplace(arch, dtype, blob, x, y, n, (int)L, status, s);
+    const bool f16 = dtype == RDN_F16;     // else, off the Tiled geometry, RDN_F16MIX
+    switch (rdn::forward_geometry(arch, dtype, n, L, rdn::device_cus(rdn::stream_device(s)),
+                                  env_override("RDN_SHORT_TILES"), env_override("RDN_WALK"))) {
+      case rdn::Geometry::Walk:
+        e = f16 ? rdn::launch_fused16_f16_walk(arch, blob, x, y, n, (int)L, status, kmo, s)
+                : rdn::launch_fused_inplace_walk(blob, x, y, n, (int)L, status, kmo, s), done = kmo != nullptr;
+        break;
+      case rdn::Geometry::Short:
+        e = f16 ? rdn::launch_fused16_f16_small(arch, blob, x, y, n, (int)L, status, s)
+                : rdn::launch_fused_inplace_short(blob, x, y, n, (int)L, status, s);
+        break;
+      case rdn::Geometry::Tiled:
+        e = dtype == RDN_BF16 ? rdn::launch_fused16(arch, blob, x, y, n, (int)L, status, s)
+            : f16             ? rdn::launch_fused16_f16(arch, blob, x, y, n, (int)L, status, s)
+                              : rdn::launch_fused_inplace(arch, dtype, blob, x, y, n, (int)L, status, s);
+        break;
+    }
   }
   if (e != hipSuccess) return hip_check(e, who);
   done = done && mo;
@@ -333,7 +317,7 @@ static int forward_status(const char* who, int arch, int dtype, int64_t n, int64
                           hipStream_t s, unsigned* flags) {
   if (flags) *flags = 0;
   if (!valid_arch(arch) || !valid_dtype(dtype)) return fail(RDN_EINVAL, std::string(who) + ": unknown arch/dtype");
-  if (n < 0 || L < 1 || L > 0x7fffffff) return fail(RDN_EINVAL, std::string(who) + ": bad n / L");
+  if (bad_rows(n, L, 1)) return fail(RDN_EINVAL, std::string(who) + ": bad n / L");
   if (unsupported(arch, dtype)) return fail_unsupported(who);
   if (!is_cbam(arch)) {
     if (!status_word(dtype) || !ws || ws_bytes < RANGE_WS_BYTES) return hip_check(hipStreamSynchronize(s), who);
@@ -404,7 +388,7 @@ int rdn_metrics(const float* y, const float* clean, int64_t n, int64_t L, double
                 void* stream) {
   RDN_GUARD_BEGIN
   if (n > 0 && (!y || !clean)) return fail(RDN_EINVAL, "rdn_metrics: null pointer");
-  if (n < 0 || L < 7 || L > 0x7fffffff) return fail(RDN_EINVAL, "rdn_metrics: need L >= 7 (SSIM window)");
+  if (bad_rows(n, L, 7)) return fail(RDN_EINVAL, "rdn_metrics: need L >= 7 (SSIM window)");
   if (n == 0) return RDN_OK;
   return hip_check(rdn::launch_metrics(y, clean, false, n, (int)L, per_spectrum, sums, nullptr, (hipStream_t)stream),
                    "metrics");
@@ -416,7 +400,7 @@ int rdn_metrics_ex(const float* y, const void* clean, int clean_is_f64, int64_t 
   RDN_GUARD_BEGIN
   if (n > 0 && (!y || !clean)) return fail(RDN_EINVAL, "rdn_metrics_ex: null pointer");
   if (clean_is_f64 != 0 && clean_is_f64 != 1) return fail(RDN_EINVAL, "rdn_metrics_ex: clean_is_f64 must be 0 or 1");
-  if (n < 0 || L < 7 || L > 0x7fffffff) return fail(RDN_EINVAL, "rdn_metrics_ex: need L >= 7 (SSIM window)");
+  if (bad_rows(n, L, 7)) return fail(RDN_EINVAL, "rdn_metrics_ex: need L >= 7 (SSIM window)");
   if (n == 0) return RDN_OK;
   return hip_check(rdn::launch_metrics(y, clean, clean_is_f64 == 1, n, (int)L, per_spectrum, sums, (long long*)acc,
                                        (hipStream_t)stream),
@@ -511,8 +495,7 @@ static int check_report_call(const std::string& fn, int64_t min_L, bool rows, in
                              const void* per, const char* per_name) {
   if (n > 0 && !rows) return fail(RDN_EINVAL, fn + ": null pointer");
   if (clean_is_f64 != 0 && clean_is_f64 != 1) return fail(RDN_EINVAL, fn + ": clean_is_f64 must be 0 or 1");
-  if (n < 0 || L < min_L || L > 0x7fffffff)
-    return fail(RDN_EINVAL, fn + ": need n >= 0 and " + std::to_string(min_L) + " <= L < 2^31");
+  if (bad_rows(n, L, min_L)) return fail(RDN_EINVAL, fn + ": need n >= 0 and " + std::to_string(min_L) + " <= L < 2^31");
   if (!weights_ok) return fail(RDN_EINVAL, fn + ": the weights alpha, beta, gamma must be finite");
   if (report && !valid_bins(lo, hi, nbins)) return fail(RDN_EINVAL, fn + ": " + bins_msg());
   if (!report && fed) return fail(RDN_EINVAL, fn + ": " + fed + " the report, which is NULL");
@@ -579,20 +562,15 @@ int rdn_physics_grad(const float* x, const float* y, const void* clean, int clea
   if (n > 0 && !(y && clean && grad)) return fail(RDN_EINVAL, fn + ": null pointer");
   if (n > 0 && per_spectrum6 && !x) return fail(RDN_EINVAL, fn + ": per_spectrum6 needs x, which is NULL");
   if (clean_is_f64 != 0 && clean_is_f64 != 1) return fail(RDN_EINVAL, fn + ": clean_is_f64 must be 0 or 1");
-  if (n < 0 || L < 3 || L > 0x7fffffff) return fail(RDN_EINVAL, fn + ": need n >= 0 and 3 <= L < 2^31");
+  if (bad_rows(n, L, 3)) return fail(RDN_EINVAL, fn + ": need n >= 0 and 3 <= L < 2^31");
   if (!(std::isfinite(alpha) && std::isfinite(beta) && std::isfinite(gamma)))
     return fail(RDN_EINVAL, fn + ": the weights alpha, beta, gamma must be finite");
   if (!std::isfinite(scale)) return fail(RDN_EINVAL, fn + ": scale must be finite");
   if (n == 0) return RDN_OK;
-  {  // every position reads its neighbours while other lanes' gradients land
-    const uintptr_t rows = (uintptr_t)n * (uintptr_t)L, gb = (uintptr_t)grad, gbytes = rows * sizeof(float);
-    const auto overlaps = [&](const void* p, uintptr_t bytes) {
-      return p && (uintptr_t)p < gb + gbytes && gb < (uintptr_t)p + bytes;
-    };
-    if (overlaps(x, rows * sizeof(float)) || overlaps(y, rows * sizeof(float)) ||
-        overlaps(clean, rows * (clean_is_f64 ? sizeof(double) : sizeof(float))))
-      return fail(RDN_EINVAL, fn + ": grad overlaps x, y or clean");
-  }
+  const size_t bytes = row_bytes(n, L);  // every position reads its neighbours while other lanes' gradients land
+  if ((x && rdn::overlaps(x, bytes, grad, bytes)) || rdn::overlaps(y, bytes, grad, bytes) ||
+      rdn::overlaps(clean, clean_is_f64 ? 2 * bytes : bytes, grad, bytes))
+    return fail(RDN_EINVAL, fn + ": grad overlaps x, y or clean");
   const rdn::phys::PhysOut po{per_spectrum6, nullptr, nullptr, rdn::Bins{0.f, 0.f, 0.f, 0}, alpha, beta, gamma, grad, scale};
   return hip_check(rdn::launch_physics(per_spectrum6 ? x : nullptr, y, clean, clean_is_f64 == 1, n, (int)L, po,
                                        (hipStream_t)stream),
@@ -616,11 +594,9 @@ static int check_filter_call(const std::string& fn, const float* x, const float*
   if (n < 0) return fail(RDN_EINVAL, fn + ": need n >= 0");
   if (w < 1 || w > RDN_FILTER_MAX_WINDOW || w % 2 == 0)
     return fail(RDN_EINVAL, fn + ": the window must be odd, 1 <= w <= " + std::to_string(RDN_FILTER_MAX_WINDOW));
-  if (L < w || L > 0x7fffffff) return fail(RDN_EINVAL, fn + ": need w <= L < 2^31");
-  if (n > 0) {  // tiles re-read their neighbours' samples (the halo) while other tiles' outputs land in y
-    const uintptr_t xb = (uintptr_t)x, yb = (uintptr_t)y, bytes = (uintptr_t)n * (uintptr_t)L * sizeof(float);
-    if (xb < yb + bytes && yb < xb + bytes) return fail(RDN_EINVAL, fn + ": x and y overlap");
-  }
+  if (bad_rows(0, L, w)) return fail(RDN_EINVAL, fn + ": need w <= L < 2^31");
+  // tiles re-read their neighbours' samples (the halo) while other tiles' outputs land in y
+  if (rdn::overlaps(x, row_bytes(n, L), y, row_bytes(n, L))) return fail(RDN_EINVAL, fn + ": x and y overlap");
   return RDN_OK;
 }
 
@@ -650,20 +626,18 @@ int rdn_haar_shrink(const float* x, float* y, double* med, int64_t n, int64_t L,
   if (levels < 1 || levels > RDN_HAAR_MAX_LEVELS)
     return fail(RDN_EINVAL, fn + ": need 1 <= levels <= " + std::to_string(RDN_HAAR_MAX_LEVELS));
   if (mode != RDN_HAAR_SOFT && mode != RDN_HAAR_HARD) return fail(RDN_EINVAL, fn + ": unknown mode " + std::to_string(mode));
-  if (L < ((int64_t)1 << levels) || L > 0x7fffffff) return fail(RDN_EINVAL, fn + ": need 2^levels <= L < 2^31");
+  if (bad_rows(0, L, (int64_t)1 << levels)) return fail(RDN_EINVAL, fn + ": need 2^levels <= L < 2^31");
   rdn::haar::Factors f = {};
   for (int j = 0; j < levels; ++j) {
     if (!std::isfinite(k[j]) || k[j] < 0.0) return fail(RDN_EINVAL, fn + ": every k must be finite and >= 0");
     f.k[j] = k[j];
   }
-  if (n > 0) {  // tiles re-read their neighbours' samples (the halo) while other tiles' outputs land in y
-    const uintptr_t xb = (uintptr_t)x, yb = (uintptr_t)y, bytes = (uintptr_t)n * (uintptr_t)L * sizeof(float);
-    if (xb < yb + bytes && yb < xb + bytes) return fail(RDN_EINVAL, fn + ": x and y overlap");
-    // med is written by the select kernel while x is still to be read, and read while y is written
-    const uintptr_t mb = (uintptr_t)med, mbytes = (uintptr_t)n * sizeof(double);
-    if ((mb < xb + bytes && xb < mb + mbytes) || (mb < yb + bytes && yb < mb + mbytes))
-      return fail(RDN_EINVAL, fn + ": med overlaps x or y");
-  }
+  const size_t bytes = row_bytes(n, L), mbytes = (size_t)n * sizeof(double);
+  // tiles re-read their neighbours' samples (the halo) while other tiles' outputs land in y
+  if (rdn::overlaps(x, bytes, y, bytes)) return fail(RDN_EINVAL, fn + ": x and y overlap");
+  // med is written by the select kernel while x is still to be read, and read while y is written
+  if (rdn::overlaps(med, mbytes, x, bytes) || rdn::overlaps(med, mbytes, y, bytes))
+    return fail(RDN_EINVAL, fn + ": med overlaps x or y");
   if (n == 0) return RDN_OK;
   return hip_check(rdn::launch_haar_shrink(x, y, med, n, (int)L, levels, f, mode, (hipStream_t)stream), "haar_shrink");
   RDN_GUARD_END

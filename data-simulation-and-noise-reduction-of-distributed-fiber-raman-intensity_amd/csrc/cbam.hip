@@ -1557,8 +1557,6 @@ static int dtype_mode(int dtype) {
   return dtype == F32 ? ip::MODE_F32 : dtype == BF16X3 ? ip::MODE_X3 : dtype == F16F8 ? ip::MODE_H8
        : dtype == F16 ? ip::MODE_F16 : ip::MODE_B1;
 }
-// attribute slots 40-49 (team kernels) and 64-68 (segment kernels), host_util.hpp
-static int team_slot(int arch, int mode) { return mode == MODE_P16 ? 80 + (arch == ADSDN) : 40 + 2 * mode + (arch == ADSDN); }
 static const void* team_fn(int arch, int mode) {
   return mode == MODE_P16 ? (const void*)team16_kernel(arch) : (const void*)team_kernel(arch, mode);
 }
@@ -1568,7 +1566,7 @@ static int team_mode(int dtype) { return dtype == F16 ? MODE_P16 : dtype_mode(dt
 
 static int team_blocks_query(int arch, int mode, int dev) {
   const void* k = team_fn(arch, mode);
-  if (ensure_dynamic_lds(k, team_slot(arch, mode), team_lds(mode), dev) != hipSuccess) {
+  if (ensure_dynamic_lds(k, team_lds(mode), dev) != hipSuccess) {
     (void)hipGetLastError();          // no team geometry (the segment path runs); leave no sticky error behind
     return 0;
   }
@@ -1584,13 +1582,13 @@ static int team_blocks_query(int arch, int mode, int dev) {
 // device): the occupancy query ran three times per call of the batch-1 loop (the forward's workspace
 // check and launch, the status read)
 static int team_blocks_per_cu(int arch, int mode, int dev) {
-  static std::atomic<int> known[MAX_DEVICES * ATTR_SLOTS];           // blocks + 1; 0 = not queried yet
-  const int slot = team_slot(arch, mode);
-  if (dev < 0 || dev >= MAX_DEVICES) return 0;
-  const int c = known[dev * ATTR_SLOTS + slot].load(std::memory_order_relaxed);
+  static std::atomic<int> known[MAX_DEVICES][2][MODE_P16 + 1];       // [dev][ADSDN?][mode]: blocks + 1; 0 = not queried yet
+  if (dev < 0 || dev >= MAX_DEVICES || mode < 0 || mode > MODE_P16) return 0;
+  std::atomic<int>& k = known[dev][arch == ADSDN][mode];
+  const int c = k.load(std::memory_order_relaxed);
   if (c > 0) return c - 1;
   const int nb = team_blocks_query(arch, mode, dev);
-  known[dev * ATTR_SLOTS + slot].store(nb + 1, std::memory_order_relaxed);
+  k.store(nb + 1, std::memory_order_relaxed);
   return nb;
 }
 
@@ -1636,7 +1634,7 @@ static unsigned* team_err(const TeamGeo& g, void* ws) { return (unsigned*)(team_
 static hipError_t launch_team(int arch, int mode, const TeamGeo& g, const uint8_t* blob, const float* x, float* y,
                               int64_t n, int L, void* ws, hipStream_t stream) {
   using namespace cb;
-  const hipError_t ea = ensure_dynamic_lds(team_fn(arch, mode), team_slot(arch, mode), team_lds(mode), stream_device(stream));
+  const hipError_t ea = ensure_dynamic_lds(team_fn(arch, mode), team_lds(mode), stream_device(stream));
   if (ea != hipSuccess) return ea;
   char* base = team_base(ws);
   TeamArgs ta{};
@@ -1706,7 +1704,7 @@ hipError_t launch_cbam_forward(int arch, int dtype, const uint8_t* blob, const f
                          : mode == ip::MODE_H8 ? segment<ip::MODE_H8>
                          : mode == ip::MODE_F16 ? segment<ip::MODE_F16> : segment<ip::MODE_B1>;
   const int dev = stream_device(stream);
-  const hipError_t ea = ensure_dynamic_lds((const void*)k, 64 + mode, (int)SEG_LDS_BYTES, dev);
+  const hipError_t ea = ensure_dynamic_lds((const void*)k, (int)SEG_LDS_BYTES, dev);
   if (ea != hipSuccess) return ea;
   const int tmode = team_mode(dtype);
   const TeamGeo tg = team_geo(arch, tmode, L, dev);

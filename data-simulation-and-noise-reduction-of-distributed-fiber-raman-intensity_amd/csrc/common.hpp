@@ -107,7 +107,6 @@ __host__ __device__ constexpr int h16_channel(int slot, int j) {
   return 32 * (slot >> 2) + 4 * (slot & 3) + (j & 3) + 16 * (j >> 2);
 }
 
-
 // ---- LDS image ------------------------------------------------------------------------------
 // bf16 activation buffer: ROWS x 128 B, 16-B slots XOR-swizzled by (row & 7): conflict-free
 // ds_read_b128 B-fragment reads for any row offset, 2-way ds_write_b64 epilogue stores.
@@ -172,12 +171,5 @@ inline MetricOut chunk(const MetricOut* mo, int64_t n0, int L) {
                    mo->sums, mo->acc};
 }
 }  // namespace met
-
-struct Geometry {       // tiling of one launch
-  int L;                // spectrum length
-  int T;                // output positions per tile (WB - 2*halo)
-  int tiles;            // tiles per spectrum
-  int halo;
-};
 
 }  // namespace rdn

@@ -236,7 +236,7 @@ hipError_t launch_fir(const float* x, float* y, int64_t n, int L, const double* 
   return launch_chunks(n, [&](int64_t n0, int64_t nn) {
     hipLaunchKernelGGL(filt::fir_kernel, dim3((unsigned)(nn * tiles)), dim3(filt::THREADS), 0, stream, x + n0 * L,
                        y + n0 * L, L, tiles, taps, w, w > 1 ? edge_taps : nullptr);
-  }, filt::chunk_spectra(L));
+  }, tiles_chunk(tiles));
 }
 
 hipError_t launch_median(const float* x, float* y, int64_t n, int L, int w, hipStream_t stream) {
@@ -246,7 +246,7 @@ hipError_t launch_median(const float* x, float* y, int64_t n, int L, int w, hipS
     const float* xx = x + n0 * L;
     float* yy = y + n0 * L;
     filt::launch_median_w<3>(w, grid, block, stream, xx, yy, L, tiles);
-  }, filt::chunk_spectra(L));
+  }, tiles_chunk(tiles));
 }
 
 }  // namespace rdn

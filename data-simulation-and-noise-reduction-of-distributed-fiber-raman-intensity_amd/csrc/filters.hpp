@@ -28,12 +28,6 @@ constexpr int STAGE_WORDS = lds_at(STAGE) + 1;
 static_assert(TILE == RDN_FILTER_TILE, "the header's tile is the kernel's");
 static_assert(MAX_W % 2 == 1 && MAX_H < TILE, "a spectrum's first h outputs lie in its first tile");
 
-// spectra of one launch: their tiles fill grid.x
-inline int64_t chunk_spectra(int64_t L) {
-  const int64_t tiles = (L + TILE - 1) / TILE;
-  return 0x7fffffff / tiles;
-}
-
 }  // namespace filt
 
 hipError_t launch_fir(const float* x, float* y, int64_t n, int L, const double* taps, int w, const double* edge_taps,

@@ -145,17 +145,13 @@ hipError_t H16_LAUNCH(int arch, const uint8_t* blob, const float* x, float* y, i
     case PIDN: k = H16_NS::pidn; break;
     default: return hipErrorInvalidValue;
   }
-  // attribute slots 0-7 (bf16) / 56-63 (f16), host_util.hpp
-  const hipError_t e = ensure_dynamic_lds((const void*)k, H16_ATTR_SLOT0 + arch, (int)H16_NS::LDS_BYTES, stream_device(stream));
+  const hipError_t e = ensure_dynamic_lds((const void*)k, (int)H16_NS::LDS_BYTES, stream_device(stream));
   if (e != hipSuccess) return e;
   const int H = fused_halo(arch), T = H16_NS::WB - 2 * H, tiles = (L + T - 1) / T;
-  const int64_t chunk = (int64_t)(0x7fffffff / tiles);
-  for (int64_t n0 = 0; n0 < n; n0 += chunk) {
-    const int64_t nn = n - n0 < chunk ? n - n0 : chunk;
+  return launch_chunks(n, [&](int64_t n0, int64_t nn) {
     hipLaunchKernelGGL(k, dim3((unsigned)(nn * tiles)), dim3(H16_NS::THREADS), H16_NS::LDS_BYTES, stream, blob,
                        x + n0 * L, y + n0 * L, L, T, tiles, status);
-  }
-  return hipGetLastError();
+  }, tiles_chunk(tiles));
 }
 
 #else  // H16_WALK_T
@@ -341,15 +337,13 @@ hipError_t H16_LAUNCH(int arch, const uint8_t* blob, const float* x, float* y, i
   }
   constexpr uint32_t lds_bytes = H16_NS::LDS_BYTES;
   static_assert(lds_bytes == (uint32_t)H16_NS::WALK_MET_LDS, "launched with the LDS the metric epilogue was compiled for");
-  const hipError_t e = ensure_dynamic_lds((const void*)k, H16_ATTR_SLOT0 + arch, (int)lds_bytes, stream_device(stream));
+  const hipError_t e = ensure_dynamic_lds((const void*)k, (int)lds_bytes, stream_device(stream));
   if (e != hipSuccess) return e;
   const int ntiles = (int)(((int64_t)L + shift + H16_NS::WT - 1) / H16_NS::WT);
-  for (int64_t n0 = 0; n0 < n; n0 += 0x7fffffff) {
-    const int64_t nn = n - n0 < 0x7fffffff ? n - n0 : 0x7fffffff;
+  return launch_chunks(n, [&](int64_t n0, int64_t nn) {
     hipLaunchKernelGGL(k, dim3((unsigned)nn), dim3(H16_NS::THREADS), lds_bytes, stream, blob, x + n0 * L,
                        y + n0 * L, L, ntiles, status, met::chunk(mo, n0, L));
-  }
-  return hipGetLastError();
+  });
 }
 
 #endif  // H16_WALK_T

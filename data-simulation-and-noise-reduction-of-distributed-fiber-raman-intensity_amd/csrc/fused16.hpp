@@ -46,11 +46,9 @@
 #if RDN_H16_F16
 #define H16_NS h16f
 #define H16_LAUNCH launch_fused16_f16
-#define H16_ATTR_SLOT0 56
 #else
 #define H16_NS h16
 #define H16_LAUNCH launch_fused16
-#define H16_ATTR_SLOT0 0
 #endif
 #endif
 // big-layer stride and bias offset of the blob this instantiation reads: the fused16 layout

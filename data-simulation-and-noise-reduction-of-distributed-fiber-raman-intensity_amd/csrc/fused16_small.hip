@@ -6,6 +6,5 @@
 #define RDN_H16_F16 1
 #define H16_NS h16fs
 #define H16_LAUNCH launch_fused16_f16_small
-#define H16_ATTR_SLOT0 84
 #define H16_TILE_ROWS 256
 #include "fused16.hip"

@@ -5,6 +5,5 @@
 #define RDN_H16_F16 1
 #define H16_NS h16fw
 #define H16_LAUNCH launch_fused16_f16_walk
-#define H16_ATTR_SLOT0 100
 #define H16_WALK_T H16_WALK_ROWS
 #include "fused16.hip"

@@ -477,16 +477,13 @@ static fused_kernel_t pick(int arch) {
 hipError_t launch_fused_inplace_short(const uint8_t* blob, const float* x, float* y, int64_t n, int L,
                                       unsigned* status, hipStream_t stream) {
   const fused_kernel_t k = ip::rrcdnet_short<ip::RRCDNET_F16MIX_TAIL>;
-  const hipError_t e = ensure_dynamic_lds((const void*)k, 92, (int)ip::TileGeo<2>::LDS, stream_device(stream));
+  const hipError_t e = ensure_dynamic_lds((const void*)k, (int)ip::TileGeo<2>::LDS, stream_device(stream));
   if (e != hipSuccess) return e;
   const int H = fused_halo(RRCDNET), T = ip::TileGeo<2>::WB - 2 * H, tiles = (L + T - 1) / T;
-  const int64_t chunk = (int64_t)(0x7fffffff / tiles);
-  for (int64_t n0 = 0; n0 < n; n0 += chunk) {
-    const int64_t nn = n - n0 < chunk ? n - n0 : chunk;
+  return launch_chunks(n, [&](int64_t n0, int64_t nn) {
     hipLaunchKernelGGL(k, dim3((unsigned)(nn * tiles)), dim3(THREADS), ip::TileGeo<2>::LDS, stream, blob, x + n0 * L,
                        y + n0 * L, L, T, tiles, status);
-  }
-  return hipGetLastError();
+  }, tiles_chunk(tiles));
 }
 
 // RDN_F16MIX RRCDNet on the walk geometry (ip::rrcdnet_hybrid_walk): one workgroup per spectrum
@@ -496,17 +493,14 @@ hipError_t launch_fused_inplace_walk(const uint8_t* blob, const float* x, float*
   const auto k = met ? ip::rrcdnet_hybrid_walk<ip::RRCDNET_F16MIX_TAIL, true> : ip::rrcdnet_hybrid_walk<ip::RRCDNET_F16MIX_TAIL, false>;
   constexpr uint32_t lds_bytes = ip::TileGeo<5>::LDS;   // the tiled hybrid's 640 rows (a spiked spectrum) fill it
   static_assert(lds_bytes == (uint32_t)ip::HYB_WALK_LDS, "launched with the LDS the kernel and its metric epilogue were compiled for");
-  // attribute slots 93 / 94, host_util.hpp
-  const hipError_t e = ensure_dynamic_lds((const void*)k, met ? 94 : 93, (int)lds_bytes, stream_device(stream));
+  const hipError_t e = ensure_dynamic_lds((const void*)k, (int)lds_bytes, stream_device(stream));
   if (e != hipSuccess) return e;
   const int H = fused_halo(RRCDNET), T = ip::TileGeo<5>::WB - 2 * H, tiles = (L + T - 1) / T;
   const int ntiles = (int)(((int64_t)L + walk_shift(RRCDNET) + RDN_WALK_ROWS_MIX - 1) / RDN_WALK_ROWS_MIX);
-  for (int64_t n0 = 0; n0 < n; n0 += 0x7fffffff) {
-    const int64_t nn = n - n0 < 0x7fffffff ? n - n0 : 0x7fffffff;
+  return launch_chunks(n, [&](int64_t n0, int64_t nn) {
     hipLaunchKernelGGL(k, dim3((unsigned)nn), dim3(THREADS), lds_bytes, stream, blob, x + n0 * L, y + n0 * L, L, T, tiles,
                        ntiles, status, met::chunk(mo, n0, L));
-  }
-  return hipGetLastError();
+  });
 }
 
 // dtype: F32 (exact fp32), BF16X3 (split bf16) or F16F8 (f16 + e4m3 correction); see common.hpp
@@ -522,18 +516,13 @@ hipError_t launch_fused_inplace(int arch, int dtype, const uint8_t* blob, const 
   const int nbk = arch == DSDN ? ip::NetGeo<DSDN>::NBK : ip::NetGeo<RRCDNET>::NBK;
   const int wb = 128 * nbk;
   const uint32_t lds = nbk == 4 ? ip::TileGeo<4>::LDS : ip::TileGeo<5>::LDS;
-  // attribute slots 8-39 and 70-77 (RDN_F16MIX), host_util.hpp
-  const int slot = dtype == F16MIX ? 70 + arch : 8 + dtype * 8 + arch;
-  const hipError_t e = ensure_dynamic_lds((const void*)k, slot, (int)lds, stream_device(stream));
+  const hipError_t e = ensure_dynamic_lds((const void*)k, (int)lds, stream_device(stream));
   if (e != hipSuccess) return e;
   const int H = fused_halo(arch), T = wb - 2 * H, tiles = (L + T - 1) / T;
-  const int64_t chunk = (int64_t)(0x7fffffff / tiles);
-  for (int64_t n0 = 0; n0 < n; n0 += chunk) {
-    const int64_t nn = n - n0 < chunk ? n - n0 : chunk;
+  return launch_chunks(n, [&](int64_t n0, int64_t nn) {
     hipLaunchKernelGGL(k, dim3((unsigned)(nn * tiles)), dim3(THREADS), lds, stream, blob, x + n0 * L,
                        y + n0 * L, L, T, tiles, status);
-  }
-  return hipGetLastError();
+  }, tiles_chunk(tiles));
 }
 
 }  // namespace rdn

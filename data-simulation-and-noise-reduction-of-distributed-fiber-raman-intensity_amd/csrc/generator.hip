@@ -11,6 +11,7 @@
 // Float transforms are written under `fp contract(off)` (and the file is built with
 // -ffp-contract=off) so that no FMA fusion makes them differ from the float32 numpy restatement.
 #include "common.hpp"
+#include "host_util.hpp"
 
 // Every float op below is rounded on its own, exactly like the numpy restatement: no FMA fusion.
 #pragma clang fp contract(off)
@@ -188,13 +189,10 @@ hipError_t launch_generate(uint64_t seed, uint64_t first, int64_t n, int L, floa
                            float extreme_prob, int max_repeat, float* clean, float* noisy, float* snr,
                            float* nstd, hipStream_t stream) {
   const gen::Params prm{L, snr_lo, snr_hi, extreme_prob, max_repeat};
-  const int64_t chunk = 0x7fffffff;
-  for (int64_t n0 = 0; n0 < n; n0 += chunk) {
-    const int64_t nn = n - n0 < chunk ? n - n0 : chunk;
+  return launch_chunks(n, [&](int64_t n0, int64_t nn) {
     hipLaunchKernelGGL(gen::generate_kernel, dim3((unsigned)nn), dim3(gen::GT), 0, stream, seed, first + n0, prm,
                        clean + n0 * L, noisy + n0 * L, snr ? snr + n0 : nullptr, nstd ? nstd + n0 : nullptr);
-  }
-  return hipGetLastError();
+  });
 }
 
 }  // namespace rdn

@@ -238,7 +238,7 @@ hipError_t launch_haar_shrink(const float* x, float* y, double* med, int64_t n, 
       hipLaunchKernelGGL(haar::shrink_kernel<RDN_HAAR_HARD>, grid, block, lds, stream, xx, yy, mm, L, tiles, levels, k);
     else
       hipLaunchKernelGGL(haar::shrink_kernel<RDN_HAAR_SOFT>, grid, block, lds, stream, xx, yy, mm, L, tiles, levels, k);
-  }, haar::chunk_spectra(L));
+  }, tiles_chunk(tiles));
 }
 
 }  // namespace rdn

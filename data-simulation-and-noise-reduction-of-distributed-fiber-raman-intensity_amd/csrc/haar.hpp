@@ -31,12 +31,6 @@ static_assert(shrink_lds_bytes(MAX_LEVELS) <= 64 * 1024, "the shrink kernel's pl
 static_assert(SELECT_LDS_L * sizeof(float) <= 48 * 1024, "the select kernel's row is static LDS");
 static_assert(MAX_H < TILE, "a halo is shorter than a tile");
 
-// spectra of one launch: their tiles fill grid.x
-inline int64_t chunk_spectra(int64_t L) {
-  const int64_t tiles = (L + TILE - 1) / TILE;
-  return 0x7fffffff / tiles;
-}
-
 }  // namespace haar
 
 hipError_t launch_haar_shrink(const float* x, float* y, double* med, int64_t n, int L, int levels,

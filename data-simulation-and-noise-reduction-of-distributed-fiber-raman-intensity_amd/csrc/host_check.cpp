@@ -11,16 +11,25 @@
 // simulator's parameter bounds (rdn_generate with n = 0); and the
 // host side of the SNR report (rdn_snr's argument checks, rdn_report_bin, rdn_report_value on an
 // exactly-sized report) and of the PhysicsAwareLoss report (rdn_physics's argument checks,
-// rdn_physics_value); and the argument checks of the baseline filters (rdn_fir, rdn_median).
+// rdn_physics_value); and the argument checks of the baseline filters (rdn_fir, rdn_median), of
+// rdn_haar_shrink and of rdn_physics_grad (every refusal, each overlap pair, n = 0 succeeding).
+// And the pure host helpers of the launch path, which no device test can reach: the once-per-(kernel,
+// device) bookkeeping of the LDS opt-in with a counting fake setter (host_util.hpp once_per: repeats,
+// device bounds, a failing setter, 8 racing threads, a full table), the chunk walk (for_chunks,
+// tiles_chunk: 2^33 workgroups in 5 launches), overlaps(), and the forward's geometry choice
+// (geometry.hpp forward_geometry) against values derived by hand from its formulas.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/raman_mi355x.h"
+#include "geometry.hpp"
+#include "host_util.hpp"
 
 static int fails = 0;
 #define EXPECT(c)                                                     \
@@ -30,6 +39,185 @@ static int fails = 0;
       ++fails;                                                        \
     }                                                                 \
   } while (0)
+
+// the last error names the check that refused
+static bool refused(int rc, const char* what) { return rc == RDN_EINVAL && std::strstr(rdn_last_error(), what); }
+
+static void check_once_per() {
+  using rdn::once_per;
+  static char kernels[rdn::OnceTable::CAPACITY + 2];      // distinct addresses stand in for kernels
+  int calls = 0;
+  const auto ok = [&] { ++calls; return hipSuccess; };
+  {
+    rdn::OnceTable t;
+    EXPECT(once_per(t, &kernels[0], 0, ok) == hipSuccess && once_per(t, &kernels[0], 0, ok) == hipSuccess && calls == 1);
+    EXPECT(once_per(t, &kernels[1], 0, ok) == hipSuccess && calls == 2);                 // another kernel, same device
+    EXPECT(once_per(t, &kernels[0], 63, ok) == hipSuccess && calls == 3);                // same kernel, devices 0 and 63
+    EXPECT(once_per(t, &kernels[0], 63, ok) == hipSuccess && once_per(t, &kernels[1], 0, ok) == hipSuccess && calls == 3);
+    EXPECT(once_per(t, &kernels[0], -1, ok) == hipErrorInvalidValue && once_per(t, &kernels[0], 64, ok) == hipErrorInvalidValue);
+    EXPECT(once_per(t, nullptr, 0, ok) == hipErrorInvalidValue && calls == 3);
+    // a setter that fails once is asked again, then never again
+    int tries = 0;
+    const auto flaky = [&] { return ++tries == 1 ? hipErrorInvalidValue : hipSuccess; };
+    EXPECT(once_per(t, &kernels[2], 5, flaky) == hipErrorInvalidValue && tries == 1);
+    EXPECT(once_per(t, &kernels[2], 5, flaky) == hipSuccess && tries == 2);
+    EXPECT(once_per(t, &kernels[2], 5, flaky) == hipSuccess && tries == 2);
+    EXPECT(t.used.load() == 3);
+  }
+  {  // 8 threads race on one pair: one set, and every thread sees success
+    rdn::OnceTable t;
+    std::atomic<int> sets{0}, good{0}, go{0};
+    std::vector<std::thread> th;
+    for (int i = 0; i < 8; ++i)
+      th.emplace_back([&] {
+        while (!go.load()) {}
+        for (int r = 0; r < 100; ++r)
+          good += once_per(t, &kernels[0], 7, [&] { ++sets; return hipSuccess; }) == hipSuccess;
+      });
+    go = 1;
+    for (auto& x : th) x.join();
+    EXPECT(sets.load() == 1 && good.load() == 800);
+  }
+  {  // a full table refuses a new kernel (without calling the setter) and still serves the ones it holds
+    rdn::OnceTable t;
+    calls = 0;
+    for (int i = 0; i < rdn::OnceTable::CAPACITY; ++i) EXPECT(once_per(t, &kernels[i], 1, ok) == hipSuccess);
+    EXPECT(calls == rdn::OnceTable::CAPACITY);
+    EXPECT(once_per(t, &kernels[rdn::OnceTable::CAPACITY], 1, ok) != hipSuccess && calls == rdn::OnceTable::CAPACITY);
+    EXPECT(once_per(t, &kernels[rdn::OnceTable::CAPACITY - 1], 2, ok) == hipSuccess && calls == rdn::OnceTable::CAPACITY + 1);
+  }
+}
+
+static void check_chunks() {
+  // the calls are contiguous from 0, none is empty or exceeds `chunk`, and they end at n
+  const auto walk = [](int64_t n, int64_t chunk) {
+    int64_t next = 0, calls = 0;
+    bool good = true;
+    rdn::for_chunks(n, chunk, [&](int64_t n0, int64_t nn) {
+      good = good && n0 == next && nn >= 1 && nn <= chunk;
+      next = n0 + nn;
+      ++calls;
+    });
+    return good && next == (n > 0 ? n : 0) ? calls : (int64_t)-1;
+  };
+  EXPECT(walk(0, 7) == 0);
+  EXPECT(walk(7, 7) == 1);
+  EXPECT(walk(8, 7) == 2);
+  EXPECT(walk(1, 0x7fffffff) == 1);
+  EXPECT(walk((int64_t)1 << 33, 0x7fffffff) == 5);         // 4 (2^31 - 1) = 2^33 - 4: a fifth launch of 4
+  EXPECT(rdn::tiles_chunk(18) * 18 <= 0x7fffffff && (rdn::tiles_chunk(18) + 1) * 18 > 0x7fffffff);
+  EXPECT(rdn::tiles_chunk(1) == 0x7fffffff);
+}
+
+static void check_overlaps() {
+  char b[64];
+  EXPECT(rdn::overlaps(b, 16, b, 16));
+  EXPECT(!rdn::overlaps(b, 16, b + 16, 16) && !rdn::overlaps(b + 16, 16, b, 16));     // end to start
+  EXPECT(rdn::overlaps(b, 17, b + 16, 16) && rdn::overlaps(b + 16, 16, b, 17));       // one byte, from the left
+  EXPECT(rdn::overlaps(b, 16, b + 15, 16) && rdn::overlaps(b + 15, 16, b, 16));       // ... from the right
+  EXPECT(!rdn::overlaps(b + 8, 0, b, 16) && !rdn::overlaps(b, 16, b + 8, 0) && !rdn::overlaps(b, 0, b, 0));
+}
+
+static void check_forward_geometry() {
+  using G = rdn::Geometry;
+  const auto geo = [](int dtype, int64_t n, int64_t L, int64_t cus = 256, int so = -1, int wo = -1) {
+    return rdn::forward_geometry(RDN_RRCDNET, dtype, n, L, cus, so, wo);
+  };
+  // RRCDNet: halo 29, so a 640-row tile owns T = 582 positions and L = 10,000 is 18 tiles (17 T = 9894);
+  // its walk is wt = ceil((10,000 + 28) / 576) = 18 tiles of 576 rows.  256 CUs.
+  for (int dtype : {RDN_F16MIX, RDN_F16}) {
+    EXPECT(geo(dtype, 1, 10000) == G::Short);              // 2 * 1 * 18 = 36 <= 256
+    EXPECT(geo(dtype, 7, 10000) == G::Short);              // 2 * 7 * 18 = 252 <= 256
+    // 2 * 8 * 18 = 288 > 256; walk ceil(8 / 256) * 18 * 576 = 10,368 rows against ceil(144 / 256) * 640 = 640
+    EXPECT(geo(dtype, 8, 10000) == G::Tiled);
+    // walk ceil(8192 / 256) = 32 rounds * 18 * 576 = 331,776 < ceil(147,456 / 256) = 576 rounds * 640 = 368,640
+    EXPECT(geo(dtype, 8192, 10000) == G::Walk);
+    // L = 7 is one tile: 2 * 128 = 256 <= 256; 2 * 129 = 258 > 256, and then the walk's one round of
+    // ceil(35 / 576) = 1 tile, 576 rows, is below the tile's one round of 640
+    EXPECT(geo(dtype, 128, 7) == G::Short);
+    EXPECT(geo(dtype, 129, 7) == G::Walk);
+    // no CU count: Tiled
+    for (int64_t n : {1, 7, 8, 8192}) EXPECT(geo(dtype, n, 10000, 0) == G::Tiled);
+    // RDN_SHORT_TILES: 1 forces Short where the rule says Walk, 0 refuses it where the rule says Short (n = 1
+    // is then Tiled: 10,368 walk rows against 640)
+    EXPECT(geo(dtype, 8192, 10000, 256, 1) == G::Short && geo(dtype, 8192, 10000, 0, 1) == G::Short);
+    EXPECT(geo(dtype, 1, 10000, 256, 0) == G::Tiled);
+    // RDN_WALK: 1 forces Walk where the rule says Tiled (also without a CU count), 0 refuses it where the
+    // rule says Walk; Short is tested first
+    EXPECT(geo(dtype, 8, 10000, 256, -1, 1) == G::Walk && geo(dtype, 8, 10000, 0, -1, 1) == G::Walk);
+    EXPECT(geo(dtype, 8192, 10000, 256, -1, 0) == G::Tiled);
+    EXPECT(geo(dtype, 1, 10000, 256, -1, 1) == G::Short && geo(dtype, 1, 10000, 256, 0, 1) == G::Walk);
+  }
+  // the other dtypes have the one geometry, whatever the overrides say
+  for (int dtype : {RDN_BF16, RDN_F32, RDN_BF16X3, RDN_F16F8})
+    for (int64_t n : {1, 7, 8, 8192}) EXPECT(geo(dtype, n, 10000) == G::Tiled && geo(dtype, n, 10000, 256, 1, 1) == G::Tiled);
+}
+
+// rdn_haar_shrink and rdn_physics_grad: every refusal comes before any HIP call (each call below is
+// refused or has n = 0), in the order the checks have always been reported in
+static void check_haar_and_grad_args() {
+  std::vector<float> buf(256, 0.f);
+  float* b = buf.data();
+  const double k3[3] = {1.0, 0.5, 0.25};
+  const double inf = INFINITY, nan = NAN;
+  {
+    const auto haar = [&](const float* x, float* y, double* med, int64_t n, int64_t L, int levels, const double* k,
+                          int mode = RDN_HAAR_HARD) { return rdn_haar_shrink(x, y, med, n, L, levels, k, mode, nullptr); };
+    double* med = (double*)(b + 128);
+    EXPECT(refused(haar(b, b + 32, med, 1, 16, 3, nullptr), "null pointer"));
+    EXPECT(refused(haar(nullptr, nullptr, nullptr, 0, 16, 3, nullptr), "null pointer"));   // k: for n = 0 too
+    EXPECT(refused(haar(nullptr, b + 32, med, 1, 16, 3, k3), "null pointer"));
+    EXPECT(refused(haar(b, nullptr, med, 1, 16, 3, k3), "null pointer"));
+    EXPECT(refused(haar(b, b + 32, nullptr, 1, 16, 3, k3), "null pointer"));
+    EXPECT(refused(haar(b, b + 32, med, -1, 16, 3, k3), "need n >= 0"));
+    EXPECT(refused(haar(b, b + 32, med, 1, 16, 0, k3), "levels"));
+    EXPECT(refused(haar(b, b + 32, med, 1, 1 << 10, RDN_HAAR_MAX_LEVELS + 1, k3), "levels"));
+    EXPECT(refused(haar(b, b + 32, med, 1, 16, 3, k3, 2), "unknown mode 2"));
+    EXPECT(refused(haar(b, b + 32, med, 1, 16, 3, k3, -1), "unknown mode -1"));
+    EXPECT(refused(haar(b, b + 32, med, 1, 7, 3, k3), "2^levels <= L"));
+    EXPECT(refused(haar(nullptr, nullptr, nullptr, 0, (int64_t)1 << 31, 3, k3), "2^levels <= L"));
+    for (double bad : {nan, inf, -inf, -1.0}) {
+      const double k[3] = {1.0, 0.5, bad};
+      EXPECT(refused(haar(b, b + 32, med, 1, 16, 3, k), "every k"));
+    }
+    const double k2[3] = {1.0, 0.5, nan};                  // entries past `levels` are not read
+    EXPECT(haar(nullptr, nullptr, nullptr, 0, 16, 2, k2) == RDN_OK);
+    EXPECT(refused(haar(b, b + 15, med, 1, 16, 3, k3), "x and y overlap"));
+    EXPECT(refused(haar(b + 15, b, med, 1, 16, 3, k3), "x and y overlap"));
+    EXPECT(refused(haar(b, b + 32, (double*)(b + 14), 1, 16, 3, k3), "med overlaps"));     // the last 8 bytes of x
+    EXPECT(refused(haar(b, b + 32, (double*)(b + 32), 1, 16, 3, k3), "med overlaps"));     // the first 8 of y
+    EXPECT(haar(nullptr, nullptr, nullptr, 0, 16, 3, k3) == RDN_OK);
+    EXPECT(haar(nullptr, nullptr, nullptr, 0, ((int64_t)1 << 31) - 1, 3, k3, RDN_HAAR_SOFT) == RDN_OK);
+  }
+  {
+    std::vector<double> per(6, 0.0);
+    const auto grad = [&](const float* x, const float* y, const void* clean, int f64, int64_t n, int64_t L, float* g,
+                          double alpha = 0.1, double scale = 1.0, double* per6 = nullptr) {
+      return rdn_physics_grad(x, y, clean, f64, n, L, alpha, 0.05, 0.01, scale, per6, g, nullptr);
+    };
+    // n = 1, L = 16: x at 0, y at 16, clean at 32 (fp64: floats 32 .. 63), grad at 64
+    EXPECT(refused(grad(b, nullptr, b + 32, 0, 1, 16, b + 64), "null pointer"));
+    EXPECT(refused(grad(b, b + 16, nullptr, 0, 1, 16, b + 64), "null pointer"));
+    EXPECT(refused(grad(b, b + 16, b + 32, 0, 1, 16, nullptr), "null pointer"));
+    EXPECT(refused(grad(nullptr, b + 16, b + 32, 0, 1, 16, b + 64, 0.1, 1.0, per.data()), "per_spectrum6 needs x"));
+    EXPECT(refused(grad(b, b + 16, b + 32, 2, 1, 16, b + 64), "clean_is_f64"));
+    EXPECT(refused(grad(b, b + 16, b + 32, 0, -1, 16, b + 64), "3 <= L < 2^31"));
+    EXPECT(refused(grad(b, b + 16, b + 32, 0, 1, 2, b + 64), "3 <= L < 2^31"));
+    EXPECT(refused(grad(nullptr, nullptr, nullptr, 0, 0, (int64_t)1 << 31, nullptr), "3 <= L < 2^31"));
+    EXPECT(refused(grad(b, b + 16, b + 32, 0, 1, 16, b + 64, nan), "weights"));
+    EXPECT(refused(grad(b, b + 16, b + 32, 0, 1, 16, b + 64, inf), "weights"));
+    EXPECT(refused(grad(b, b + 16, b + 32, 0, 1, 16, b + 64, 0.1, nan), "scale must be finite"));
+    EXPECT(refused(grad(b, b + 16, b + 32, 0, 1, 16, b + 64, 0.1, -inf), "scale must be finite"));
+    EXPECT(refused(grad(b, b + 16, b + 32, 0, 1, 16, b + 15), "grad overlaps"));           // x's last sample
+    EXPECT(refused(grad(b, b + 16, b + 32, 0, 1, 16, b + 1), "grad overlaps"));            // x and y
+    EXPECT(refused(grad(nullptr, b + 16, b + 32, 0, 1, 16, b + 31), "grad overlaps"));     // y's last sample (no x)
+    EXPECT(refused(grad(b, b + 16, b + 32, 0, 1, 16, b + 47), "grad overlaps"));           // fp32 clean's last sample
+    EXPECT(refused(grad(b, b + 16, b + 32, 1, 1, 16, b + 48), "grad overlaps"));           // fp64 clean's second half
+    EXPECT(refused(grad(b, b + 16, b + 32, 1, 1, 16, b + 63), "grad overlaps"));
+    EXPECT(grad(nullptr, nullptr, nullptr, 0, 0, 16, nullptr) == RDN_OK);
+    EXPECT(grad(nullptr, nullptr, nullptr, 1, 0, ((int64_t)1 << 31) - 1, nullptr, 0.1, 1.0, per.data()) == RDN_OK);
+  }
+}
 
 int main(int argc, char** argv) {
   if (argc != 5) {
@@ -213,6 +401,12 @@ int main(int argc, char** argv) {
     EXPECT(rdn_median(nullptr, nullptr, 0, 16, 5, nullptr) == RDN_OK);
     EXPECT(std::strlen(rdn_last_error()) > 0);
   }
+
+  check_haar_and_grad_args();
+  check_once_per();
+  check_chunks();
+  check_overlaps();
+  check_forward_geometry();
 
   if (fails) return 1;
   std::printf("host_check: arch %d dtype %d: %zu tensors, %zu bytes packed, all checks passed\n", arch, dtype,

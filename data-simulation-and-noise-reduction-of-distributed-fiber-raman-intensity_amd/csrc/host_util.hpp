@@ -2,12 +2,13 @@
 //
 // The ABI is re-entrant (include/raman_mi355x.h): launches may come from several threads and for
 // streams of different devices.  hipFuncSetAttribute(MaxDynamicSharedMemorySize) and the CU count
-// are per device, so both caches are keyed by the device that owns the launch stream and guarded
-// by one mutex (taken once per (kernel, device) pair on the slow path; lock-free afterwards).
+// are per device, so both caches are keyed by the device that owns the launch stream (the opt-in by the
+// kernel too) and guarded by one mutex (taken once per (kernel, device) pair on the slow path; lock-free afterwards).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstdint>
 #include <cstring>
 #include <mutex>
 
@@ -26,36 +27,63 @@ inline int stream_device(hipStream_t s) {
   return dev;
 }
 
-// One flag per (kernel slot, device).  `slot` is a small per-launcher index (< 64) naming the
-// kernel function; callers own disjoint slot ranges (see the launchers).
-inline std::mutex& attr_mutex() {
-  static std::mutex m;
-  return m;
-}
-constexpr int ATTR_SLOTS = 128;
-inline std::atomic<bool>* attr_flags() {
-  static std::atomic<bool> f[ATTR_SLOTS * MAX_DEVICES];
-  return f;
+// Once per (kernel, device): the bookkeeping of ensure_dynamic_lds, apart from its HIP call.  The key is
+// the kernel's host address: an append-only table of {kernel, one bit per device}, scanned without a lock
+// (an entry is published by `used`, a device's bit by `devices`) and appended under the mutex.
+struct OnceTable {
+  static constexpr int CAPACITY = 256;      // kernels that ever asked (about 60 take the LDS opt-in)
+  struct Entry {
+    const void* fn = nullptr;
+    std::atomic<uint64_t> devices{0};
+  };
+  static_assert(MAX_DEVICES <= 64, "one bit per device");
+  Entry entries[CAPACITY];
+  std::atomic<int> used{0};
+  std::mutex mutex;
+};
+
+// set() for the pair (fn, dev), unless an earlier set() for it succeeded: a failed one leaves the pair
+// unset, so the next call tries again.  A full table is an error (the opt-in is never skipped).
+template <class Set>
+inline hipError_t once_per(OnceTable& t, const void* fn, int dev, Set set) {
+  if (!fn || dev < 0 || dev >= MAX_DEVICES) return hipErrorInvalidValue;
+  const uint64_t bit = (uint64_t)1 << dev;
+  const auto find = [&](int used) -> OnceTable::Entry* {
+    for (int i = 0; i < used; ++i)
+      if (t.entries[i].fn == fn) return &t.entries[i];
+    return nullptr;
+  };
+  OnceTable::Entry* e = find(t.used.load(std::memory_order_acquire));
+  if (e && (e->devices.load(std::memory_order_acquire) & bit)) return hipSuccess;
+  std::lock_guard<std::mutex> lock(t.mutex);
+  const int used = t.used.load(std::memory_order_relaxed);
+  if (!e && !(e = find(used))) {
+    if (used == OnceTable::CAPACITY) return hipErrorOutOfMemory;
+    e = &t.entries[used];
+    e->fn = fn;
+    t.used.store(used + 1, std::memory_order_release);
+  }
+  if (e->devices.load(std::memory_order_relaxed) & bit) return hipSuccess;
+  const hipError_t err = set();
+  if (err == hipSuccess) e->devices.fetch_or(bit, std::memory_order_release);
+  return err;
 }
 
 // Allow `bytes` of dynamic LDS for kernel `fn` on device `dev` (once per pair).
-inline hipError_t ensure_dynamic_lds(const void* fn, int slot, int bytes, int dev) {
-  if (slot < 0 || slot >= ATTR_SLOTS || dev < 0 || dev >= MAX_DEVICES) return hipErrorInvalidValue;
-  std::atomic<bool>& flag = attr_flags()[dev * ATTR_SLOTS + slot];
-  if (flag.load(std::memory_order_acquire)) return hipSuccess;
-  std::lock_guard<std::mutex> lock(attr_mutex());
-  if (flag.load(std::memory_order_relaxed)) return hipSuccess;
-  int cur = 0;
-  hipError_t e = hipGetDevice(&cur);
-  if (e != hipSuccess) return e;
-  if (cur != dev && (e = hipSetDevice(dev)) != hipSuccess) return e;
-  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (cur != dev) {
-    const hipError_t e2 = hipSetDevice(cur);
-    if (e == hipSuccess) e = e2;
-  }
-  if (e == hipSuccess) flag.store(true, std::memory_order_release);
-  return e;
+inline hipError_t ensure_dynamic_lds(const void* fn, int bytes, int dev) {
+  static OnceTable table;
+  return once_per(table, fn, dev, [&] {
+    int cur = 0;
+    hipError_t e = hipGetDevice(&cur);
+    if (e != hipSuccess) return e;
+    if (cur != dev && (e = hipSetDevice(dev)) != hipSuccess) return e;
+    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (cur != dev) {
+      const hipError_t e2 = hipSetDevice(cur);
+      if (e == hipSuccess) e = e2;
+    }
+    return e;
+  });
 }
 
 // Copy `bytes` (<= 16) of status words from the device to `out` behind the work on `s` and wait for
@@ -87,13 +115,28 @@ inline hipError_t with_clean(const void* clean, bool clean_f64, F f) {
   return clean_f64 ? f((const double*)clean) : f((const float*)clean);
 }
 
+// [0, n) in consecutive pieces of at most `chunk`: f(n0, nn) for the nn that start at n0.
+template <class F>
+inline void for_chunks(int64_t n, int64_t chunk, F f) {
+  for (int64_t n0 = 0; n0 < n; n0 += chunk) f(n0, n - n0 < chunk ? n - n0 : chunk);
+}
+
+// spectra of one launch of a kernel that runs `tiles` workgroups per spectrum: their tiles fill grid.x
+inline int64_t tiles_chunk(int64_t tiles) { return 0x7fffffff / tiles; }
+
 // Walks a batch of n workgroups (one per spectrum) in launches of at most 2^31 - 1, the grid's limit in
 // x: launch(n0, nn) enqueues the nn of them that start at n0.  (`chunk`: fewer spectra per launch, for a
-// kernel that runs several workgroups per spectrum.)
+// kernel that runs several workgroups per spectrum: tiles_chunk.)
 template <class Launch>
 inline hipError_t launch_chunks(int64_t n, Launch launch, int64_t chunk = 0x7fffffff) {
-  for (int64_t n0 = 0; n0 < n; n0 += chunk) launch(n0, n - n0 < chunk ? n - n0 : chunk);
+  for_chunks(n, chunk, launch);
   return hipGetLastError();
+}
+
+// the byte ranges [a, a + abytes) and [b, b + bbytes) share a byte (an empty range shares none)
+inline bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return abytes && bbytes && x < y + bbytes && y < x + abytes;
 }
 
 // Compute units of device `dev` (0 if the query fails), cached per device.

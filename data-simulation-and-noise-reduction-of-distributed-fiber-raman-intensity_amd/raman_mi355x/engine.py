@@ -189,6 +189,31 @@ def _check_out(t, name, shape, device, dtype=torch.float32):
         raise ValueError(f"{name} must be contiguous")
 
 
+def _no_overlap(a, b, what):
+    """ValueError(``what``) if the bytes of tensors ``a`` and ``b`` overlap (the kernels take raw pointers)."""
+    if (a.data_ptr() < b.data_ptr() + b.numel() * b.element_size()
+            and b.data_ptr() < a.data_ptr() + a.numel() * a.element_size()):
+        raise ValueError(what)
+
+
+def _check_rows_input(x):
+    """x as the filters take it: a float32 CUDA tensor, (N, L) or (N, 1, L), contiguous."""
+    _check_cuda_f32(x, "input")
+    if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[1] != 1):
+        raise ValueError(f"expected (N, L) or (N, 1, L) input, got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError("input must be contiguous")
+
+
+def _out_like(x, out):
+    """The output of a launch that reads x: ``out``, checked to be x's shape and apart from it, or a new tensor."""
+    if out is None:
+        return torch.empty_like(x)
+    _check_out(out, "out", x.shape, x.device)
+    _no_overlap(out, x, "out must not overlap the input (tiles re-read input halos while outputs are written)")
+    return out
+
+
 def needs_workspace(arch, code):
     """A forward of (arch, code) takes a workspace: the CBAM team kernels (required) and the fused
     networks' 16-bit dtypes (their status word: range and input gate)."""
@@ -226,7 +251,7 @@ class Workspace:
 
     @property
     def ptr(self):
-        return ctypes.c_void_p(self.buf.data_ptr() if self.buf is not None else 0)
+        return _ptr(self.buf)
 
     def fits(self, arch, code, n, L, device):
         """Made for this network, dtype, length and device, large enough for n spectra, and bound to the
@@ -294,11 +319,7 @@ def _forward_args(arch, dtype, x, out, check, workspace, _ws_checked):
         raise ValueError(f"expected (N, 1, L) input, got {tuple(x.shape)}")
     n, L = x.shape[0], x.shape[-1]
     a, code = _arch(arch), resolve_dtype(arch, dtype)
-    y = torch.empty_like(x) if out is None else out
-    if out is not None:
-        _check_out(y, "out", x.shape, x.device)
-    if y.data_ptr() < x.data_ptr() + x.numel() * 4 and x.data_ptr() < y.data_ptr() + y.numel() * 4:
-        raise ValueError("out must not overlap the input (tiles re-read input halos while outputs are written)")
+    y = _out_like(x, out)
     ws = workspace
     if ws is None and (a in CBAM_IDS or (check and code in RANGE_CODES)):
         ws = Workspace(a, code, n, L, x.device)
@@ -329,11 +350,9 @@ def forward(arch, dtype, packed, x, out=None, check=True, workspace=None, _ws_ch
     _check_cuda_f32(x, "input")
     x = x.contiguous()
     n, L, a, code, y, ws = _forward_args(arch, dtype, x, out, check, workspace, _ws_checked)
-    L_ = _lib.lib()
-    _lib.check(L_.rdn_forward(a, code, ctypes.c_void_p(packed.data_ptr()), ctypes.c_void_p(x.data_ptr()),
-                              ctypes.c_void_p(y.data_ptr()), n, L,
-                              ws.ptr if ws is not None else ctypes.c_void_p(0), ws.bytes if ws is not None else 0,
-                              _stream(x.device)), "rdn_forward")
+    _lib.check(_lib.lib().rdn_forward(a, code, _ptr(packed), _ptr(x), _ptr(y), n, L,
+                                      ws.ptr if ws is not None else _ptr(None), ws.bytes if ws is not None else 0,
+                                      _stream(x.device)), "rdn_forward")
     if check and ws is not None:
         ws.check()
     return y
@@ -364,12 +383,9 @@ def forward_metrics(arch, dtype, packed, x, clean, out=None, sums=None, per_spec
         _check_out(acc, "acc", (_lib.ACC_WORDS,), x.device, torch.int64)
     fused = ctypes.c_int(0)
     _lib.check(_lib.lib().rdn_forward_metrics(
-        a, code, ctypes.c_void_p(packed.data_ptr()), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()), n, L,
-        ctypes.c_void_p(clean.data_ptr()), int(clean.dtype == torch.float64),
-        ctypes.c_void_p(per.data_ptr() if per is not None else 0), ctypes.c_void_p(sums.data_ptr()),
-        ctypes.c_void_p(acc.data_ptr() if acc is not None else 0),
-        ws.ptr if ws is not None else ctypes.c_void_p(0), ws.bytes if ws is not None else 0, _stream(x.device),
-        ctypes.byref(fused)), "rdn_forward_metrics")
+        a, code, _ptr(packed), _ptr(x), _ptr(y), n, L, _ptr(clean), int(clean.dtype == torch.float64), _ptr(per),
+        _ptr(sums), _ptr(acc), ws.ptr if ws is not None else _ptr(None), ws.bytes if ws is not None else 0,
+        _stream(x.device), ctypes.byref(fused)), "rdn_forward_metrics")
     if check and ws is not None:
         ws.check()
     return y, per, sums, bool(fused.value)
@@ -458,12 +474,8 @@ def metrics(y, clean, sums=None, per_spectrum=True, acc=None):
         _check_out(sums, "sums", (5,), y.device, torch.float64)   # fp64 atomics into sums[0..4]
     if acc is not None:
         _check_out(acc, "acc", (_lib.ACC_WORDS,), y.device, torch.int64)
-    _lib.check(_lib.lib().rdn_metrics_ex(ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(clean.data_ptr()),
-                                         int(clean.dtype == torch.float64), n, L,
-                                         ctypes.c_void_p(per.data_ptr() if per is not None else 0),
-                                         ctypes.c_void_p(sums.data_ptr()),
-                                         ctypes.c_void_p(acc.data_ptr() if acc is not None else 0),
-                                         _stream(y.device)), "rdn_metrics_ex")
+    _lib.check(_lib.lib().rdn_metrics_ex(_ptr(y), _ptr(clean), int(clean.dtype == torch.float64), n, L, _ptr(per),
+                                         _ptr(sums), _ptr(acc), _stream(y.device)), "rdn_metrics_ex")
     return per, sums
 
 
@@ -693,22 +705,13 @@ FILTER_MAX_WINDOW = _lib.FILTER_MAX_WINDOW
 
 def _filter_args(x, window, out):
     """What fir() and median() do with x, the window and ``out`` before the launch: (x, y, n, L)."""
-    _check_cuda_f32(x, "input")
-    if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[1] != 1):
-        raise ValueError(f"expected (N, L) or (N, 1, L) input, got {tuple(x.shape)}")
-    if not x.is_contiguous():
-        raise ValueError("input must be contiguous")
+    _check_rows_input(x)
     if isinstance(window, bool) or int(window) != window or not 1 <= int(window) <= FILTER_MAX_WINDOW or window % 2 == 0:
         raise ValueError(f"the window must be an odd integer in [1, {FILTER_MAX_WINDOW}], got {window!r}")
     n, L = x.shape[0], x.shape[-1]
     if L < window:
         raise ValueError(f"spectra of {L} samples are shorter than the window {window}")
-    y = torch.empty_like(x) if out is None else out
-    if out is not None:
-        _check_out(y, "out", x.shape, x.device)
-    if y.data_ptr() < x.data_ptr() + x.numel() * 4 and x.data_ptr() < y.data_ptr() + y.numel() * 4:
-        raise ValueError("out must not overlap the input (tiles re-read input halos while outputs are written)")
-    return x, y, n, L
+    return x, _out_like(x, out), n, L
 
 
 def _device_taps(t, name, shape, device):
@@ -762,11 +765,7 @@ def haar_shrink(x, k, mode="hard", out=None, med=None):
     and >= 0 (wavelets.haar_thresholds).  Returns (y, med): y float32 of x's shape, med float64 (N,), m per
     spectrum; a spectrum with a NaN or an infinity gives NaN in both.  ``out`` / ``med``: buffers to write into
     (made when None); out must not overlap x, and med neither of them."""
-    _check_cuda_f32(x, "input")
-    if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[1] != 1):
-        raise ValueError(f"expected (N, L) or (N, 1, L) input, got {tuple(x.shape)}")
-    if not x.is_contiguous():
-        raise ValueError("input must be contiguous")
+    _check_rows_input(x)
     if mode not in HAAR_MODES:
         raise ValueError(f"mode must be 'soft' or 'hard', got {mode!r}")
     k = [float(v) for v in (k.tolist() if hasattr(k, "tolist") else k)]
@@ -778,17 +777,12 @@ def haar_shrink(x, k, mode="hard", out=None, med=None):
     n, L = x.shape[0], x.shape[-1]
     if L < 2 ** J:
         raise ValueError(f"spectra of {L} samples are shorter than 2^{J}, the reach of {J} levels")
-    y = torch.empty_like(x) if out is None else out
-    if out is not None:
-        _check_out(y, "out", x.shape, x.device)
-    if y.data_ptr() < x.data_ptr() + x.numel() * 4 and x.data_ptr() < y.data_ptr() + y.numel() * 4:
-        raise ValueError("out must not overlap the input (tiles re-read input halos while outputs are written)")
+    y = _out_like(x, out)
     m = torch.empty(n, dtype=torch.float64, device=x.device) if med is None else med
     if med is not None:
         _check_out(m, "med", (n,), x.device, torch.float64)
         for t, name in ((x, "the input"), (y, "out")):
-            if m.data_ptr() < t.data_ptr() + t.numel() * 4 and t.data_ptr() < m.data_ptr() + m.numel() * 8:
-                raise ValueError(f"med must not overlap {name}")
+            _no_overlap(m, t, f"med must not overlap {name}")
     _lib.check(_lib.lib().rdn_haar_shrink(_ptr(x), _ptr(y), _ptr(m), n, L, J, (ctypes.c_double * J)(*k), HAAR_MODES[mode],
                                           _stream(x.device)), "rdn_haar_shrink")
     return y, m

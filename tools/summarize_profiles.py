@@ -18,7 +18,7 @@ import os
 import shutil
 import sys
 
-# round 5: batch 8192 runs the walk kernels (abi.cpp walk_tiles)
+# round 5: batch 8192 runs the walk kernels (geometry.hpp forward_geometry)
 KERNELS = {"f16": "rdn::ip::rrcdnet_hybrid_walk<5, false>", "f16-plain": "rdn::h16fw::rrcdnet_walk", "f16f8": "rdn::ip::rrcdnet<3, 0>",
            "bf16x3": "rdn::ip::rrcdnet<2, 0>", "bf16-unsafe": "rdn::h16::rrcdnet"}
 # scripts/gpu_final.sh passes: pmc_<arch>-<dtype>_<counter>, batch per arch

@@ -1,6 +1,6 @@
 """A/B of the walk geometry (fused16_walk.hip) against the 640-row tiles, in one process on one GPU.
 
-Times engine.forward with RDN_WALK=0 / 1 interleaved (the knob is read per call, abi.cpp walk_tiles)
+Times engine.forward with RDN_WALK=0 / 1 interleaved (the knob is read per call, geometry.hpp forward_geometry)
 on on-device simulator spectra, and checks the two outputs are bitwise equal.
 
     python tools/walk_ab.py [--batch 8192] [--L 10000] [net:dtype ...]    (default DenoiseCNN:f16 RRCDNet:f16-plain)
