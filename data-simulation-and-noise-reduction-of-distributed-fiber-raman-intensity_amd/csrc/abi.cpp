@@ -16,6 +16,7 @@
 #include "physics.hpp"
 #include "filters.hpp"
 #include "haar.hpp"
+#include "potts.hpp"
 
 namespace rdn {
 std::string pack(int arch, int dtype, const float* const* tensors, const int64_t* numels, int n, void* dst, size_t cap);
@@ -640,6 +641,43 @@ int rdn_haar_shrink(const float* x, float* y, double* med, int64_t n, int64_t L,
     return fail(RDN_EINVAL, fn + ": med overlaps x or y");
   if (n == 0) return RDN_OK;
   return hip_check(rdn::launch_haar_shrink(x, y, med, n, (int)L, levels, f, mode, (hipStream_t)stream), "haar_shrink");
+  RDN_GUARD_END
+}
+
+int rdn_noise_mad(const float* x, double* med, int64_t n, int64_t L, void* stream) {
+  RDN_GUARD_BEGIN
+  const std::string fn = "rdn_noise_mad";
+  if (n > 0 && !(x && med)) return fail(RDN_EINVAL, fn + ": null pointer");
+  if (bad_rows(n, L, 1)) return fail(RDN_EINVAL, fn + ": need n >= 0 and 1 <= L < 2^31");
+  // med is written while other spectra of x are still to be read
+  if (rdn::overlaps(med, (size_t)n * sizeof(double), x, row_bytes(n, L))) return fail(RDN_EINVAL, fn + ": med overlaps x");
+  if (n == 0) return RDN_OK;
+  return hip_check(rdn::launch_noise_mad(x, med, n, (int)L, (hipStream_t)stream), "noise_mad");
+  RDN_GUARD_END
+}
+
+int rdn_potts(const float* x, float* y, int32_t* nseg, const double* gamma, int64_t n, int64_t L, int max_len,
+              uint8_t* work, size_t work_bytes, void* stream) {
+  RDN_GUARD_BEGIN
+  const std::string fn = "rdn_potts";
+  if (!gamma) return fail(RDN_EINVAL, fn + ": null gamma");
+  if (n < 0) return fail(RDN_EINVAL, fn + ": need n >= 0");
+  if (max_len < 1 || max_len > RDN_POTTS_MAX_LEN)
+    return fail(RDN_EINVAL, fn + ": need 1 <= max_len <= " + std::to_string(RDN_POTTS_MAX_LEN));
+  if (bad_rows(0, L, 1)) return fail(RDN_EINVAL, fn + ": need 1 <= L < 2^31");
+  if (n == 0) return RDN_OK;
+  if (!(x && y && work)) return fail(RDN_EINVAL, fn + ": null pointer");
+  if ((uint64_t)n > (uint64_t)SIZE_MAX / (uint64_t)L / sizeof(float) || work_bytes < (size_t)n * (size_t)L)
+    return fail(RDN_EINVAL, fn + ": work_bytes is below n * L");
+  const size_t bytes = row_bytes(n, L), sbytes = (size_t)n * sizeof(int32_t);
+  if (rdn::overlaps(x, bytes, y, bytes)) return fail(RDN_EINVAL, fn + ": x and y overlap");
+  // the back-pointers land in work while x is still to be read, and are read while y is written
+  if (rdn::overlaps(work, work_bytes, x, bytes) || rdn::overlaps(work, work_bytes, y, bytes))
+    return fail(RDN_EINVAL, fn + ": work overlaps x or y");
+  if (nseg && (rdn::overlaps(nseg, sbytes, x, bytes) || rdn::overlaps(nseg, sbytes, y, bytes) ||
+               rdn::overlaps(nseg, sbytes, work, work_bytes)))
+    return fail(RDN_EINVAL, fn + ": nseg overlaps x, y or work");
+  return hip_check(rdn::launch_potts(x, y, nseg, gamma, n, (int)L, max_len, work, (hipStream_t)stream), "potts");
   RDN_GUARD_END
 }
 

@@ -241,4 +241,13 @@ hipError_t launch_haar_shrink(const float* x, float* y, double* med, int64_t n, 
   }, tiles_chunk(tiles));
 }
 
+// m alone (rdn_noise_mad): the select kernel of launch_haar_shrink, launched the same way
+hipError_t launch_noise_mad(const float* x, double* med, int64_t n, int L, hipStream_t stream) {
+  return launch_chunks(n, [&](int64_t n0, int64_t nn) {
+    const dim3 block(haar::THREADS), rows((unsigned)nn);
+    if (L <= haar::SELECT_LDS_L) hipLaunchKernelGGL(haar::select_kernel<true>, rows, block, 0, stream, x + n0 * L, med + n0, L);
+    else hipLaunchKernelGGL(haar::select_kernel<false>, rows, block, 0, stream, x + n0 * L, med + n0, L);
+  });
+}
+
 }  // namespace rdn

@@ -35,5 +35,7 @@ static_assert(MAX_H < TILE, "a halo is shorter than a tile");
 
 hipError_t launch_haar_shrink(const float* x, float* y, double* med, int64_t n, int L, int levels,
                               const haar::Factors& k, int mode, hipStream_t s);
+// the median |d_1| of each spectrum alone: the select kernel of launch_haar_shrink, any L >= 1
+hipError_t launch_noise_mad(const float* x, double* med, int64_t n, int L, hipStream_t s);
 
 }  // namespace rdn

@@ -12,7 +12,8 @@
 // host side of the SNR report (rdn_snr's argument checks, rdn_report_bin, rdn_report_value on an
 // exactly-sized report) and of the PhysicsAwareLoss report (rdn_physics's argument checks,
 // rdn_physics_value); and the argument checks of the baseline filters (rdn_fir, rdn_median), of
-// rdn_haar_shrink and of rdn_physics_grad (every refusal, each overlap pair, n = 0 succeeding).
+// rdn_haar_shrink, of rdn_physics_grad, and of rdn_potts and rdn_noise_mad (every refusal, each overlap pair,
+// n = 0 succeeding).
 // And the pure host helpers of the launch path, which no device test can reach: the once-per-(kernel,
 // device) bookkeeping of the LDS opt-in with a counting fake setter (host_util.hpp once_per: repeats,
 // device bounds, a failing setter, 8 racing threads, a full table), the chunk walk (for_chunks,
@@ -219,6 +220,61 @@ static void check_haar_and_grad_args() {
   }
 }
 
+// rdn_potts and rdn_noise_mad: likewise every refusal, each overlap pair, n = 0 succeeding
+static void check_potts_and_mad_args() {
+  std::vector<float> buf(512, 0.f);
+  float* b = buf.data();
+  {
+    // n = 1, L = 16: x at floats 0 .. 15, y at 16 .. 31, work (16 bytes) at float 32, nseg at 40, gamma at 64
+    uint8_t* const w = (uint8_t*)(b + 32);
+    int32_t* const s = (int32_t*)(b + 40);
+    const double* const g = (const double*)(b + 64);
+    const auto potts = [&](const float* x, float* y, int32_t* nseg, const double* gamma, int64_t n, int64_t L, int K,
+                           uint8_t* work, size_t wb) { return rdn_potts(x, y, nseg, gamma, n, L, K, work, wb, nullptr); };
+    EXPECT(refused(potts(b, b + 16, s, nullptr, 1, 16, 64, w, 16), "null gamma"));
+    EXPECT(refused(potts(nullptr, nullptr, nullptr, nullptr, 0, 16, 64, nullptr, 0), "null gamma"));   // for n = 0 too
+    EXPECT(refused(potts(b, b + 16, s, g, -1, 16, 64, w, 16), "need n >= 0"));
+    for (int K : {0, -1, RDN_POTTS_MAX_LEN + 1}) {
+      EXPECT(refused(potts(b, b + 16, s, g, 1, 16, K, w, 16), "max_len"));
+      EXPECT(refused(potts(nullptr, nullptr, nullptr, g, 0, 16, K, nullptr, 0), "max_len"));
+    }
+    for (int64_t L : {(int64_t)0, (int64_t)-3, (int64_t)1 << 31}) {
+      EXPECT(refused(potts(b, b + 16, s, g, 1, L, 64, w, (size_t)1 << 40), "1 <= L < 2^31"));
+      EXPECT(refused(potts(nullptr, nullptr, nullptr, g, 0, L, 64, nullptr, 0), "1 <= L < 2^31"));
+    }
+    EXPECT(refused(potts(nullptr, b + 16, s, g, 1, 16, 64, w, 16), "null pointer"));
+    EXPECT(refused(potts(b, nullptr, s, g, 1, 16, 64, w, 16), "null pointer"));
+    EXPECT(refused(potts(b, b + 16, s, g, 1, 16, 64, nullptr, 16), "null pointer"));
+    EXPECT(refused(potts(b, b + 16, s, g, 1, 16, 64, w, 15), "work_bytes"));
+    EXPECT(refused(potts(b, b + 32, s, g, 2, 16, 64, (uint8_t*)(b + 100), 31), "work_bytes"));
+    EXPECT(refused(potts(b, b + 15, s, g, 1, 16, 64, w, 16), "x and y overlap"));
+    EXPECT(refused(potts(b + 15, b, s, g, 1, 16, 64, w, 16), "x and y overlap"));
+    EXPECT(refused(potts(b, b + 16, s, g, 1, 16, 64, (uint8_t*)(b + 16) - 1, 16), "work overlaps"));   // x's last byte
+    EXPECT(refused(potts(b, b + 16, s, g, 1, 16, 64, (uint8_t*)(b + 32) - 1, 16), "work overlaps"));   // y's last byte
+    EXPECT(refused(potts(b + 100, b + 16, s, g, 1, 16, 64, (uint8_t*)(b + 16) - 15, 16), "work overlaps"));  // y's first
+    EXPECT(refused(potts(b, b + 16, (int32_t*)(b + 15), g, 1, 16, 64, w, 16), "nseg overlaps"));       // x
+    EXPECT(refused(potts(b, b + 16, (int32_t*)(b + 31), g, 1, 16, 64, w, 16), "nseg overlaps"));       // y
+    EXPECT(refused(potts(b, b + 16, (int32_t*)(b + 35), g, 1, 16, 64, w, 16), "nseg overlaps"));       // work's last 4 bytes
+    EXPECT(refused(potts(b, b + 16, s, g, 1, 16, 64, w, 33), "nseg overlaps"));                        // the stated extent
+    EXPECT(potts(nullptr, nullptr, nullptr, g, 0, 16, 64, nullptr, 0) == RDN_OK);
+    EXPECT(potts(nullptr, nullptr, nullptr, g, 0, ((int64_t)1 << 31) - 1, 1, nullptr, 0) == RDN_OK);
+  }
+  {
+    double* med = (double*)(b + 128);
+    const auto mad = [&](const float* x, double* m, int64_t n, int64_t L) { return rdn_noise_mad(x, m, n, L, nullptr); };
+    EXPECT(refused(mad(nullptr, med, 1, 16), "null pointer"));
+    EXPECT(refused(mad(b, nullptr, 1, 16), "null pointer"));
+    EXPECT(refused(mad(b, med, -1, 16), "1 <= L < 2^31"));
+    EXPECT(refused(mad(b, med, 1, 0), "1 <= L < 2^31"));
+    EXPECT(refused(mad(nullptr, nullptr, 0, 0), "1 <= L < 2^31"));
+    EXPECT(refused(mad(nullptr, nullptr, 0, (int64_t)1 << 31), "1 <= L < 2^31"));
+    EXPECT(refused(mad(b, (double*)(b + 14), 1, 16), "med overlaps"));     // the last 8 bytes of x
+    EXPECT(refused(mad(b + 1, (double*)b, 1, 16), "med overlaps"));        // 4 bytes below x and its first 4
+    EXPECT(mad(nullptr, nullptr, 0, 1) == RDN_OK);
+    EXPECT(mad(nullptr, nullptr, 0, ((int64_t)1 << 31) - 1) == RDN_OK);
+  }
+}
+
 int main(int argc, char** argv) {
   if (argc != 5) {
     std::fprintf(stderr, "usage: host_check <arch> <dtype> <tensors.bin> <blob_out.bin>\n");
@@ -403,6 +459,7 @@ int main(int argc, char** argv) {
   }
 
   check_haar_and_grad_args();
+  check_potts_and_mad_args();
   check_once_per();
   check_chunks();
   check_overlaps();

@@ -13,6 +13,8 @@ Drop-in surfaces (reference file:line):
   MedianFilter, write_comparison                  (baselines.py, engine.fir / engine.median; no reference counterpart)
   HaarShrink, haar_thresholds                     translation-invariant Haar wavelet shrinkage with a blind per-spectrum
                                                   noise estimate (wavelets.py, engine.haar_shrink; no reference counterpart)
+  PottsFit                                        the exact piecewise-constant (jump-penalised least-squares) fit with the same
+                                                  noise estimate (potts.py, engine.potts; no reference counterpart)
 """
 from . import engine
 from .baselines import (BASELINES, GaussianSmooth, MedianFilter, MovingAverage, SavitzkyGolay, gaussian_taps,
@@ -23,6 +25,7 @@ from .distributed import all_reduce_sums, shard
 from .evaluate import evaluate, evaluate_synthetic, write_comparison, write_metrics, write_physics_report, write_snr_report
 from .models import ADSDN, APIDN, DSDN, MODELS, PIDN, DenoiseCNN, RRCDNet
 from .physics import PhysicsAwareLoss
+from .potts import PottsFit
 from .simulator import generate, generate_signals
 from .wavelets import HaarShrink, haar_thresholds
 
@@ -30,4 +33,4 @@ __all__ = ["engine", "DenoiseCNN", "RRCDNet", "DSDN", "ADSDN", "PIDN", "APIDN", 
            "generate_signals", "evaluate", "write_metrics", "write_snr_report", "load_dataset", "save_dataset", "shard",
            "all_reduce_sums", "EngineError", "RangeError", "PhysicsAwareLoss", "write_physics_report", "evaluate_synthetic",
            "write_comparison", "BASELINES", "MovingAverage", "SavitzkyGolay", "GaussianSmooth", "MedianFilter", "savgol_taps",
-           "gaussian_taps", "HaarShrink", "haar_thresholds"]
+           "gaussian_taps", "HaarShrink", "haar_thresholds", "PottsFit"]

@@ -61,6 +61,8 @@ HAAR_MAX_LEVELS = 7
 HAAR_TILE = 512
 HAAR_SELECT_LDS_L = 12288
 HAAR_SOFT, HAAR_HARD = 0, 1
+# exact piecewise-constant (Potts) fit (include/raman_mi355x.h RDN_POTTS_*)
+POTTS_MAX_LEN = 64
 
 
 def source_hash():
@@ -143,6 +145,10 @@ _SIGNATURES = {
     # translation-invariant Haar shrinkage: likewise added to ABI v6 and detected by symbol
     "rdn_haar_shrink": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                          c_double_p, ctypes.c_int, ctypes.c_void_p], ctypes.c_int),
+    # the blind noise estimate alone and the exact piecewise-constant (Potts) fit: likewise
+    "rdn_noise_mad": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
+    "rdn_potts": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                   ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGNATURES)

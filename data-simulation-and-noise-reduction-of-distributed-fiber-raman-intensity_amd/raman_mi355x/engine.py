@@ -786,3 +786,73 @@ def haar_shrink(x, k, mode="hard", out=None, med=None):
     _lib.check(_lib.lib().rdn_haar_shrink(_ptr(x), _ptr(y), _ptr(m), n, L, J, (ctypes.c_double * J)(*k), HAAR_MODES[mode],
                                           _stream(x.device)), "rdn_haar_shrink")
     return y, m
+
+
+def noise_mad(x, out=None):
+    """m of haar_shrink alone: the median of |0.5 (x[i] - x[i - 1])| over each periodic spectrum of ``x``
+    (float32 (N, L) or (N, 1, L), contiguous, CUDA; L >= 1), float64 (N,), the bits of haar_shrink's ``med``; NaN for a
+    spectrum with a NaN or an infinity (rdn_noise_mad).  ``out``: a float64 (N,) buffer to write into (made when
+    None); it must not overlap x."""
+    _check_rows_input(x)
+    n, L = x.shape[0], x.shape[-1]
+    if L < 1:
+        raise ValueError("spectra must have at least one sample")
+    m = torch.empty(n, dtype=torch.float64, device=x.device) if out is None else out
+    if out is not None:
+        _check_out(m, "out", (n,), x.device, torch.float64)
+        _no_overlap(m, x, "out must not overlap the input")
+    _lib.check(_lib.lib().rdn_noise_mad(_ptr(x), _ptr(m), n, L, _stream(x.device)), "rdn_noise_mad")
+    return m
+
+
+# ---- exact piecewise-constant (Potts) fit (rdn_potts; the arithmetic contract: include/raman_mi355x.h) ----
+POTTS_MAX_LEN = _lib.POTTS_MAX_LEN              # the longest segment: one candidate per lane of a wave
+
+
+def potts(x, gamma, max_len=POTTS_MAX_LEN, out=None, nseg=None, work=None):
+    """The jump-penalised least-squares fit of every spectrum of ``x`` (float32 (N, L) or (N, 1, L), contiguous,
+    CUDA): the segmentation into runs of at most ``max_len`` (1 to 64) samples and the run means that minimise
+    Σ (x - fit)² + gamma · #runs exactly, by dynamic programming in fp64, rounded once to fp32 (rdn_potts).
+    ``gamma``: a float64 CUDA tensor (N,), one penalty per spectrum, or a Python float for all of them.  Returns
+    (y, nseg): y float32 of x's shape, nseg int32 (N,), the number of runs.  A spectrum with a NaN or an infinity,
+    or with a negative, NaN or infinite gamma, gives NaN and 0.  ``out`` / ``nseg``: buffers to write into;
+    ``work``: uint8 scratch of at least N · L elements (each made when None).  None of them may overlap another
+    or x."""
+    _check_rows_input(x)
+    if isinstance(max_len, bool) or int(max_len) != max_len or not 1 <= int(max_len) <= POTTS_MAX_LEN:
+        raise ValueError(f"max_len must be an integer in [1, {POTTS_MAX_LEN}], got {max_len!r}")
+    n, L = x.shape[0], x.shape[-1]
+    if L < 1:
+        raise ValueError("spectra must have at least one sample")
+    if torch.is_tensor(gamma):
+        _check_out(gamma, "gamma", (n,), x.device, torch.float64)
+    else:
+        if isinstance(gamma, bool):
+            raise TypeError(f"gamma must be a float64 tensor or a float, got {gamma!r}")
+        gamma = torch.full((n,), float(gamma), dtype=torch.float64, device=x.device)
+    y = _out_like(x, out)
+    segs = torch.empty(n, dtype=torch.int32, device=x.device) if nseg is None else nseg
+    if nseg is not None:
+        _check_out(segs, "nseg", (n,), x.device, torch.int32)
+    if work is None:
+        work = torch.empty(n * L, dtype=torch.uint8, device=x.device)
+    else:
+        if not torch.is_tensor(work):
+            raise TypeError("work must be a tensor")
+        if work.dtype != torch.uint8:
+            raise TypeError(f"work must be torch.uint8, got {work.dtype}")
+        if not work.is_cuda or work.device != x.device:
+            raise ValueError(f"work must live on {x.device}, got {work.device}")
+        if not work.is_contiguous():
+            raise ValueError("work must be contiguous")
+        if work.numel() < n * L:
+            raise ValueError(f"work must have at least N * L = {n * L} elements, got {work.numel()}")
+    named = ((x, "the input"), (y, "out"), (work, "work"), (segs, "nseg"), (gamma, "gamma"))
+    for i in range(2, len(named)):               # out against the input: _out_like
+        for b, bn in named[:i]:
+            _no_overlap(named[i][0], b, f"{named[i][1]} must not overlap {bn}")
+    if n == 0:                                   # nothing to launch (an empty gamma has no address to pass)
+        return y, segs
+    _lib.check(_lib.lib().rdn_potts(_ptr(x), _ptr(y), _ptr(segs), _ptr(gamma), n, L, int(max_len), _ptr(work),
+                                    work.numel(), _stream(x.device)), "rdn_potts")
+    return y, segs

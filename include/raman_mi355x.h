@@ -482,6 +482,47 @@ enum { RDN_HAAR_SOFT = 0, RDN_HAAR_HARD = 1 };
 int rdn_haar_shrink(const float* x, float* y, double* med, int64_t n, int64_t L, int levels,
                     const double* k /* HOST [levels] */, int mode, void* stream);
 
+/* m of rdn_haar_shrink's contract alone (median over i of |0.5 * (x[i] - x[idx(i - 1)])|, periodic, numpy's
+ * median): the same select kernel, the same bits; NaN for a spectrum with a NaN or an infinity.  x: fp32 [n][L]
+ * device; med: fp64 [n] device, WRITTEN; 1 <= L < 2^31 (m = 0 for L = 1).  RDN_EINVAL, checked before any
+ * device call and also for n = 0: n < 0; L < 1 or L >= 2^31; for n > 0 a NULL x or med, or med overlapping x.
+ * n = 0 launches nothing.  No device state, no synchronisation; asynchronous on `stream`.
+ * (Added to ABI v6 without a version bump: detect by symbol.) */
+int rdn_noise_mad(const float* x, double* med, int64_t n, int64_t L, void* stream);
+
+/* ---- exact piecewise-constant (Potts) fit (added to ABI v6 without a version bump: detect by symbol) ----
+ *
+ * The jump-penalised least-squares fit of each spectrum: the segmentation into runs of at most K = max_len
+ * samples and the per-run means that minimise  sum (x - fit)^2 + g * #runs  exactly, by dynamic programming
+ * (the Potts functional; for a piecewise-constant signal under white noise of variance sigma^2, g is a small
+ * multiple of sigma^2).  x, y: fp32 [n][L] device, y WRITTEN; gamma: fp64 [n] DEVICE, g of each spectrum;
+ * nseg: int32 [n] device or NULL, WRITTEN: the number of runs; 1 <= K <= RDN_POTTS_MAX_LEN, 1 <= L < 2^31.
+ * All arithmetic is fp64, each operation rounded on its own, none fused:
+ *   S1[0] = S2[0] = 0.0;  for i = 1..L:  v = (double)x[i-1];  S1[i] = S1[i-1] + v;  S2[i] = S2[i-1] + v * v
+ *   B[0] = 0.0
+ *   for r = 1..L:  for len = 1..min(K, r), l = r - len:
+ *        d1 = S1[r] - S1[l];   d2 = S2[r] - S2[l];   sse = d2 - (d1 * d1) / (double)len     (not clamped at 0)
+ *        c(len) = (B[l] + g) + sse
+ *      B[r] = min over len of c(len);   A[r] = the SMALLEST len that attains it
+ *   r = L;  while r > 0:  len = A[r];  mean = (S1[r] - S1[r-len]) / (double)len
+ *        y[r-len .. r-1] = (float)mean  (one rounding);  nseg += 1;  r -= len
+ * A spectrum that holds a NaN or an infinity, or whose g is negative, NaN or infinite, gets the quiet NaN
+ * 0x7fc00000 at every output and nseg = 0.  A finite spectrum never produces a non-finite intermediate
+ * (fp32^2 * 2^31 fits fp64).  fp32 subnormals are read as their values.  A spectrum's output bits depend on
+ * its own samples and its own g only: not on n, its row index or the launches a huge n is split into.
+ *
+ * work: caller-owned device scratch of work_bytes >= n * L bytes, contents unspecified afterwards (the
+ * back-pointers A, one byte per position).
+ *
+ * RDN_EINVAL, checked before any device call and also for n = 0: a NULL gamma; n < 0; max_len outside
+ * [1, RDN_POTTS_MAX_LEN]; L < 1 or L >= 2^31; for n > 0 a NULL x, y or work, work_bytes < n * L, x and y
+ * overlapping, work overlapping x or y, nseg overlapping x, y or work.  n = 0 launches nothing and accepts
+ * NULL data pointers.  The library keeps no device state and never synchronises; the call is asynchronous on
+ * `stream`. */
+#define RDN_POTTS_MAX_LEN 64
+int rdn_potts(const float* x, float* y, int32_t* nseg /* may be NULL */, const double* gamma /* DEVICE [n] */,
+              int64_t n, int64_t L, int max_len, uint8_t* work, size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,13 +2,16 @@
 (DESIGN.md §5).
 
 Part 1 meters the six trained-fixture networks (tests/golden, 'trained' weights, 'f16') and a small grid of
-baseline filters (linear smoothers, running medians, translation-invariant Haar shrinkage) over the same
+baseline filters (linear smoothers, running medians, translation-invariant Haar shrinkage, the exact
+piecewise-constant fit) over the same
 on-device simulator spectra with snr_bins = (20, 37, 17), and writes the table
 to profiles/baselines/comparison.json / comparison.txt (raman_mi355x.write_comparison).
 
 Part 2 times each filter alone at L = 10 000, batch 8192, with HIP events on the launch stream, the filters
 interleaved round by round (round 0 warms up), and writes spectra/s and GB/s (80 KB of HBM traffic per
-spectrum: 40 KB read, 40 KB written) beside the HBM-bound time into profiles/baselines/throughput.json.
+spectrum: 40 KB read, 40 KB written) beside the HBM-bound time into profiles/baselines/throughput.json.  The
+piecewise-constant fit is timed as engine.potts alone, with its buffers preallocated and gamma computed before
+the clock starts; its noise estimate is the leg noise_mad.
 
     python tools/baseline_compare.py [--total 8192] [--L 10000] [--batch 2048] [--rounds 12] [--out profiles/baselines]
 """
@@ -29,8 +32,10 @@ BYTES_PER_SAMPLE = 8              # one fp32 read, one fp32 written
 
 def baseline_grid():
     from raman_mi355x import baselines as B
+    from raman_mi355x.potts import PottsFit
     from raman_mi355x.wavelets import HaarShrink
-    return {"haar4_3h": HaarShrink(), "haar3_1.5s": HaarShrink(3, 1.5, "soft"), "haar4_uni_h": HaarShrink(4, "universal"),
+    return {"potts8": PottsFit(8.0), "potts10": PottsFit(10.0), "potts12": PottsFit(), "potts16": PottsFit(16.0),
+            "potts_bic": PottsFit("bic"), "haar4_3h": HaarShrink(), "haar3_1.5s": HaarShrink(3, 1.5, "soft"), "haar4_uni_h": HaarShrink(4, "universal"),
             "ma3": B.MovingAverage(3), "ma5": B.MovingAverage(5), "sg5_2": B.SavitzkyGolay(5, 2),
             "sg21_3": B.SavitzkyGolay(21, 3), "gauss1": B.GaussianSmooth(1.0), "gauss2.5": B.GaussianSmooth(2.5),
             "med3": B.MedianFilter(3), "med5": B.MedianFilter(5), "med7": B.MedianFilter(7), "med21": B.MedianFilter(21)}
@@ -69,7 +74,13 @@ def main():
     med_buf = torch.empty(n, dtype=torch.float64, device=dev)
     legs = {k: ((lambda m=m: engine.median(x, m.window, out=y)) if isinstance(m, R.MedianFilter) else
                 (lambda m=m: engine.haar_shrink(x, m.factors(L), m.mode, out=y, med=med_buf)) if isinstance(m, R.HaarShrink) else
-                (lambda m=m: engine.fir(x, m.taps, edge_taps=m.edge_taps, out=y))) for k, m in filters.items()}
+                (lambda m=m: engine.fir(x, m.taps, edge_taps=m.edge_taps, out=y))) for k, m in filters.items()
+            if not isinstance(m, R.PottsFit)}
+    gamma = filters["potts12"].gamma(x)                                 # once, outside the timed region
+    nseg_buf = torch.empty(n, dtype=torch.int32, device=dev)
+    work = torch.empty(n * L, dtype=torch.uint8, device=dev)
+    legs["potts12"] = lambda: engine.potts(x, gamma, filters["potts12"].max_len, out=y, nseg=nseg_buf, work=work)
+    legs["noise_mad"] = lambda: engine.noise_mad(x, out=med_buf)
     legs["haar7_3h"] = lambda m=R.HaarShrink(7): engine.haar_shrink(x, m.factors(L), m.mode, out=y, med=med_buf)
     for w in (11, 25, 27, 101):                                         # sorting networks up to 25, then the radix select
         legs[f"med{w}"] = lambda w=w: engine.median(x, w, out=y)
