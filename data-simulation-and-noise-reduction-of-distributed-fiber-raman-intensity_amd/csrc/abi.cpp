@@ -17,6 +17,7 @@
 #include "filters.hpp"
 #include "haar.hpp"
 #include "potts.hpp"
+#include "blind.hpp"
 
 namespace rdn {
 std::string pack(int arch, int dtype, const float* const* tensors, const int64_t* numels, int n, void* dst, size_t cap);
@@ -472,7 +473,9 @@ static void acc_rows_value(const int64_t* words, int rows, int row_words, int qu
   }
   if (totals) row_value(total, out + (size_t)rows * values);
 }
-static_assert(RDN_ACC_WORDS <= RDN_REPORT_ROW_WORDS && RDN_PHYS_ROW_WORDS <= RDN_REPORT_ROW_WORDS, "total[]");
+static_assert(RDN_ACC_WORDS <= RDN_REPORT_ROW_WORDS && RDN_PHYS_ROW_WORDS <= RDN_REPORT_ROW_WORDS &&
+                  RDN_BLIND_ROW_WORDS <= RDN_REPORT_ROW_WORDS,
+              "total[]");
 
 int rdn_acc_value(const int64_t* acc, double* sums) {
   RDN_GUARD_BEGIN
@@ -678,6 +681,54 @@ int rdn_potts(const float* x, float* y, int32_t* nseg, const double* gamma, int6
                rdn::overlaps(nseg, sbytes, work, work_bytes)))
     return fail(RDN_EINVAL, fn + ": nseg overlaps x, y or work");
   return hip_check(rdn::launch_potts(x, y, nseg, gamma, n, (int)L, max_len, work, (hipStream_t)stream), "potts");
+  RDN_GUARD_END
+}
+
+int rdn_blind(const float* x, const float* y, const double* sigma, int64_t n, int64_t L, int lags, double q_crit,
+              double* per_spectrum7, double* rho, const float* key, float lo, float hi, int nbins, int64_t* report,
+              void* stream) {
+  RDN_GUARD_BEGIN
+  const std::string fn = "rdn_blind";
+  if (!sigma) return fail(RDN_EINVAL, fn + ": null sigma");
+  if (lags < 1 || lags > RDN_BLIND_MAX_LAGS)
+    return fail(RDN_EINVAL, fn + ": need 1 <= lags <= " + std::to_string(RDN_BLIND_MAX_LAGS));
+  if (bad_rows(n, L, (int64_t)lags + 1)) return fail(RDN_EINVAL, fn + ": need n >= 0 and lags < L < 2^31");
+  if (!(q_crit >= 0.0)) return fail(RDN_EINVAL, fn + ": q_crit must be >= 0 (+inf flags nothing)");
+  if (!per_spectrum7 && !rho && !report) return fail(RDN_EINVAL, fn + ": none of per_spectrum7, rho and report to write");
+  if (report && !valid_bins(lo, hi, nbins)) return fail(RDN_EINVAL, fn + ": " + bins_msg());
+  if (!report && key) return fail(RDN_EINVAL, fn + ": key feeds the report, which is NULL");
+  if (n == 0) return RDN_OK;
+  if (!(x && y)) return fail(RDN_EINVAL, fn + ": null pointer");
+  if ((uint64_t)n > (uint64_t)SIZE_MAX / (uint64_t)L / sizeof(double))
+    return fail(RDN_EINVAL, fn + ": n * L does not fit a size");
+  // every input is read while other spectra's outputs land: no output may share a byte with an input or
+  // with another output
+  const size_t un = (size_t)n;
+  const struct { const void* p; size_t bytes; } in[] = {{x, row_bytes(n, L)}, {y, row_bytes(n, L)},
+                                                        {sigma, un * sizeof(double)}, {key, un * sizeof(float)}},
+      out[] = {{per_spectrum7, un * RDN_BLIND_QUANTITIES * sizeof(double)}, {rho, un * (size_t)lags * sizeof(double)},
+               {report, report ? (size_t)RDN_BLIND_WORDS(nbins) * sizeof(int64_t) : 0}};
+  for (int o = 0; o < 3; ++o) {
+    if (!out[o].p) continue;
+    for (const auto& i : in)
+      if (i.p && rdn::overlaps(out[o].p, out[o].bytes, i.p, i.bytes))
+        return fail(RDN_EINVAL, fn + ": an output overlaps x, y, sigma or key");
+    for (int q = o + 1; q < 3; ++q)
+      if (out[q].p && rdn::overlaps(out[o].p, out[o].bytes, out[q].p, out[q].bytes))
+        return fail(RDN_EINVAL, fn + ": per_spectrum7, rho and report overlap");
+  }
+  const rdn::blind::BlindOut bo{per_spectrum7, rho, key, (long long*)report,
+                                report ? rdn::make_bins(lo, hi, nbins) : rdn::Bins{0.f, 0.f, 0.f, 0}, q_crit, lags};
+  return hip_check(rdn::launch_blind(x, y, sigma, n, (int)L, bo, (hipStream_t)stream), "blind");
+  RDN_GUARD_END
+}
+
+int rdn_blind_value(const int64_t* report, int nbins, double* out) {
+  RDN_GUARD_BEGIN
+  const int rc = check_report_value("rdn_blind_value", report, nbins, out);
+  if (rc != RDN_OK) return rc;
+  acc_rows_value(report, RDN_REPORT_ROWS(nbins), RDN_BLIND_ROW_WORDS, RDN_BLIND_QUANTITIES, 2, 1, true, out);
+  return RDN_OK;
   RDN_GUARD_END
 }
 

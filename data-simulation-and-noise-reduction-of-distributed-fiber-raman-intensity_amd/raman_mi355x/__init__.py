@@ -13,6 +13,9 @@ Drop-in surfaces (reference file:line):
   MedianFilter, write_comparison                  (baselines.py, engine.fir / engine.median; no reference counterpart)
   HaarShrink, haar_thresholds                     translation-invariant Haar wavelet shrinkage with a blind per-spectrum
                                                   noise estimate (wavelets.py, engine.haar_shrink; no reference counterpart)
+  evaluate_blind, evaluate(..., blind=),          residual analysis of spectra WITHOUT a clean reference (measured traces):
+  write_blind_report, blind_q_crit                residual RMS against the noise estimate, autocorrelation, Ljung-Box Q
+                                                  (engine.blind; no reference counterpart)
   PottsFit                                        the exact piecewise-constant (jump-penalised least-squares) fit with the same
                                                   noise estimate (potts.py, engine.potts; no reference counterpart)
 """
@@ -22,7 +25,8 @@ from .baselines import (BASELINES, GaussianSmooth, MedianFilter, MovingAverage, 
 from ._lib import EngineError, RangeError
 from .dataset import load_dataset, save_dataset
 from .distributed import all_reduce_sums, shard
-from .evaluate import evaluate, evaluate_synthetic, write_comparison, write_metrics, write_physics_report, write_snr_report
+from .evaluate import (blind_q_crit, evaluate, evaluate_blind, evaluate_synthetic, write_blind_report, write_comparison,
+                       write_metrics, write_physics_report, write_snr_report)
 from .models import ADSDN, APIDN, DSDN, MODELS, PIDN, DenoiseCNN, RRCDNet
 from .physics import PhysicsAwareLoss
 from .potts import PottsFit
@@ -33,4 +37,5 @@ __all__ = ["engine", "DenoiseCNN", "RRCDNet", "DSDN", "ADSDN", "PIDN", "APIDN", 
            "generate_signals", "evaluate", "write_metrics", "write_snr_report", "load_dataset", "save_dataset", "shard",
            "all_reduce_sums", "EngineError", "RangeError", "PhysicsAwareLoss", "write_physics_report", "evaluate_synthetic",
            "write_comparison", "BASELINES", "MovingAverage", "SavitzkyGolay", "GaussianSmooth", "MedianFilter", "savgol_taps",
-           "gaussian_taps", "HaarShrink", "haar_thresholds", "PottsFit"]
+           "gaussian_taps", "HaarShrink", "haar_thresholds", "PottsFit", "evaluate_blind", "blind_q_crit",
+           "write_blind_report"]

@@ -63,6 +63,19 @@ HAAR_SELECT_LDS_L = 12288
 HAAR_SOFT, HAAR_HARD = 0, 1
 # exact piecewise-constant (Potts) fit (include/raman_mi355x.h RDN_POTTS_*)
 POTTS_MAX_LEN = 64
+# blind residual report (include/raman_mi355x.h RDN_BLIND_*)
+BLIND_MAX_LAGS = 32
+BLIND_QUANTITIES = 7
+BLIND_COUNT = BLIND_QUANTITIES * ACC_STRIDE
+BLIND_FLAGGED = BLIND_COUNT + 1
+BLIND_ROW_WORDS = BLIND_FLAGGED + 1
+BLIND_VALUES = BLIND_QUANTITIES + 2
+BLIND_LDS_L = 20000
+
+
+def blind_words(nbins):
+    return report_rows(nbins) * BLIND_ROW_WORDS
+
 
 
 def source_hash():
@@ -149,6 +162,11 @@ _SIGNATURES = {
     "rdn_noise_mad": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
     "rdn_potts": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                    ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
+    # the blind residual report: likewise added to ABI v6 and detected by symbol
+    "rdn_blind": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                   ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_float,
+                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int),
+    "rdn_blind_value": ([ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
 }
 
 EXPORTED = tuple(_SIGNATURES)

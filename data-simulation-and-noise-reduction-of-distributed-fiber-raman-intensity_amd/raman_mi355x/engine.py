@@ -7,6 +7,7 @@ pointers.  Nothing here has a CPU or PyTorch-op fallback.
 import ctypes
 import math
 import os
+import statistics
 
 import torch
 
@@ -856,3 +857,97 @@ def potts(x, gamma, max_len=POTTS_MAX_LEN, out=None, nseg=None, work=None):
     _lib.check(_lib.lib().rdn_potts(_ptr(x), _ptr(y), _ptr(segs), _ptr(gamma), n, L, int(max_len), _ptr(work),
                                     work.numel(), _stream(x.device)), "rdn_potts")
     return y, segs
+
+
+# ---- blind residual report (rdn_blind; definitions and report layout: include/raman_mi355x.h) ----
+BLIND_QUANTITIES = ("Mean", "RMS", "Ratio", "Rho1", "RhoMax", "Q", "SNR_est")
+BLIND_MAX_LAGS = _lib.BLIND_MAX_LAGS
+BLIND_LDS_L = _lib.BLIND_LDS_L                  # longer spectra: pass 2 recomputes the residual through L2
+_SIGMA_PER_MAD = math.sqrt(2.0) / 0.6744897501960817  # noise_mad's m -> the noise's standard deviation
+
+
+def blind_q_crit(lags, alpha=0.01):
+    """The 1 - ``alpha`` quantile of χ² with ``lags`` degrees of freedom by Wilson and Hilferty's cube,
+    K (1 - 2/(9K) + z sqrt(2/(9K)))³ with z the normal quantile: the value a white residual's Ljung-Box Q
+    exceeds with probability ``alpha`` (within 0.2 % of the tables for 5 <= K <= 32 at alpha = 0.01)."""
+    if isinstance(lags, bool) or int(lags) != lags or not 1 <= int(lags) <= BLIND_MAX_LAGS:
+        raise ValueError(f"lags must be an integer in [1, {BLIND_MAX_LAGS}], got {lags!r}")
+    if not 0.0 < float(alpha) < 1.0:
+        raise ValueError(f"alpha must lie in (0, 1), got {alpha!r}")
+    k = float(int(lags))
+    z = statistics.NormalDist().inv_cdf(1.0 - float(alpha))
+    return k * (1.0 - 2.0 / (9.0 * k) + z * math.sqrt(2.0 / (9.0 * k))) ** 3
+
+
+def new_blind_report(nbins, device):
+    """A zeroed blind report (RDN_BLIND_WORDS(nbins) int64: nbins + 2 rows) on ``device``."""
+    return _new_report(nbins, device, _lib.blind_words)
+
+
+def blind_value(report, nbins):
+    """Doubles of a blind report (float64 (nbins + 3, 9), CPU): one row per report row -- underflow, the bins,
+    overflow -- then the totals over all of them; columns {count, ΣMean, ΣRMS, ΣRatio, ΣRho1, ΣRhoMax, ΣQ,
+    ΣSNR_est, count of flagged spectra}.  Each sum is the exact total rounded once, NaN where a value was out
+    of range (rdn_blind_value)."""
+    return _report_value(report, nbins, "blind report", _lib.blind_words, _lib.BLIND_VALUES, "rdn_blind_value")
+
+
+def blind(x, y, sigma=None, lags=16, q_crit=None, key=None, bins=None, report=None, per_spectrum=True, rho=False):
+    """What the residual r = x - y says about the denoised ``y`` without a clean reference (rdn_blind): per
+    spectrum [Mean, RMS, Ratio = RMS / sigma, Rho1, RhoMax, Q, SNR_est] (fp64, (n, 7)), with rho_k the
+    autocorrelation of the centred residual at lags 1 .. ``lags``, Q its Ljung-Box statistic and SNR_est =
+    10 log10((mean(x²) - sigma²) / sigma²) dB.  A spectrum is flagged when Q > ``q_crit`` (None:
+    blind_q_crit(lags), the χ² 0.99 quantile).  If y is the signal, Mean is 0, Ratio 1 and Q about ``lags``.
+
+    ``x``, ``y``: float32 CUDA, (N, L) or (N, 1, L), L > lags.  ``sigma``: float64 CUDA (N,), each spectrum's
+    noise level, a Python float for all of them, or None: the blind estimate noise_mad(x) · sqrt(2) /
+    0.6744897501960817 (what PottsFit.noise_std returns).  With ``bins`` = (lo, hi, nbins) the batch is also
+    added to a report binned by ``key`` (float32 (N,)), or by SNR_est when key is None; ``report``: a report
+    of new_blind_report(nbins) to accumulate into (made when None).  ``rho``: also return the (N, lags)
+    autocorrelations.  Returns (per (N, 7) or None, rho (N, lags) or None, report or None)."""
+    _check_cuda_f32(x, "input")
+    _check_cuda_f32(y, "denoised")
+    if isinstance(lags, bool) or int(lags) != lags or not 1 <= int(lags) <= BLIND_MAX_LAGS:
+        raise ValueError(f"lags must be an integer in [1, {BLIND_MAX_LAGS}], got {lags!r}")
+    lags = int(lags)
+    q_crit = blind_q_crit(lags) if q_crit is None else float(q_crit)
+    if not q_crit >= 0.0:
+        raise ValueError(f"q_crit must be >= 0 (inf flags nothing), got {q_crit!r}")
+    x, y = _rows(x), _rows(y)
+    if x.shape != y.shape:
+        raise ValueError(f"shape mismatch {tuple(x.shape)} vs {tuple(y.shape)}")
+    n, L = x.shape
+    dev = x.device
+    if y.device != dev:
+        raise ValueError(f"input on {dev} but denoised on {y.device}")
+    if L <= lags:
+        raise ValueError(f"spectra must be longer than lags = {lags}, got L = {L}")
+    if bins is None:
+        if key is not None or report is not None:
+            raise ValueError("key and report belong to the binned report: pass bins=(lo, hi, nbins)")
+        if not (per_spectrum or rho):
+            raise ValueError("nothing to compute: per_spectrum=False, rho=False and no bins")
+        lo, hi, nbins = 0.0, 0.0, 0
+    else:
+        lo, hi, nbins = _bins(bins)
+        if report is None:
+            report = _new_report(nbins, dev, _lib.blind_words)
+        else:
+            _check_out(report, "report", (_lib.blind_words(nbins),), dev, torch.int64)
+        if key is not None:
+            _check_out(key, "key", (n,), dev, torch.float32)
+    if sigma is None:
+        sigma = noise_mad(x) * _SIGMA_PER_MAD
+    elif torch.is_tensor(sigma):
+        _check_out(sigma, "sigma", (n,), dev, torch.float64)
+    else:
+        if isinstance(sigma, bool):
+            raise TypeError(f"sigma must be a float64 tensor, a float or None, got {sigma!r}")
+        sigma = torch.full((n,), float(sigma), dtype=torch.float64, device=dev)
+    per = torch.empty((n, len(BLIND_QUANTITIES)), dtype=torch.float64, device=dev) if per_spectrum else None
+    rhos = torch.empty((n, lags), dtype=torch.float64, device=dev) if rho else None
+    if n == 0:                                   # nothing to launch (an empty sigma has no address to pass)
+        return per, rhos, report
+    _lib.check(_lib.lib().rdn_blind(_ptr(x), _ptr(y), _ptr(sigma), n, L, lags, q_crit, _ptr(per), _ptr(rhos), _ptr(key),
+                                    lo, hi, nbins, _ptr(report), _stream(dev)), "rdn_blind")
+    return per, rhos, report

@@ -99,7 +99,7 @@ def snr_summary(report, bins):
 
 PHYS_KEYS = engine.PHYS_QUANTITIES
 # keys of a result that write_metrics leaves to write_snr_report / write_physics_report
-_EXTRA_RESULT_KEYS = _SNR_RESULT_KEYS + ("physics",)
+_EXTRA_RESULT_KEYS = _SNR_RESULT_KEYS + ("physics", "blind")
 
 
 def _physics_weights(physics):
@@ -132,6 +132,53 @@ def physics_summary(report, weights, L, bins=None):
         return e
 
     out = entry(v[nbins + 2], {"weights": list(weights)})
+    if out["count"] <= 0:
+        raise ValueError("no spectra were evaluated")
+    if bins is not None:
+        rows = [entry(row, {"lo": e_lo, "hi": e_hi}) for row, e_lo, e_hi in _bin_rows(v, bins)]
+        out["by_snr"], out["under"], out["over"] = rows[1:-1], rows[0], rows[-1]
+    return out
+
+
+BLIND_KEYS = engine.BLIND_QUANTITIES
+blind_q_crit = engine.blind_q_crit
+
+
+def _blind_options(blind):
+    """``blind`` of evaluate(): None / False -> None, True -> 16 lags at alpha = 0.01, a dict with ``lags``
+    and / or ``alpha`` -> those.  Returns (lags, alpha, q_crit) or None."""
+    if blind is None or blind is False:
+        return None
+    opts = {} if blind is True else dict(blind)
+    unknown = set(opts) - {"lags", "alpha"}
+    if unknown:
+        raise ValueError(f"blind takes 'lags' and 'alpha', got {sorted(unknown)}")
+    lags, alpha = opts.get("lags", 16), opts.get("alpha", 0.01)
+    return int(lags), float(alpha), blind_q_crit(lags, alpha)
+
+
+def blind_summary(report, options, bins=None):
+    """The ``"blind"`` entry of a result, from an (all-reduced) blind report (engine.blind) and ``options`` =
+    (lags, alpha, q_crit): those three, the ``count`` of spectra, the means of Mean, RMS, Ratio, Rho1, RhoMax,
+    Q and SNR_est over all of them and ``flagged_fraction``, the share whose Q exceeded q_crit.  If the
+    denoised output is the signal, Mean is 0, Ratio about 1 (0.95 against the blind noise estimate on the
+    simulator), Q about ``lags`` and flagged_fraction about alpha plus the share of spiked spectra.  With
+    ``bins`` = (lo, hi, nbins): ``by_snr``, one such entry per bin with its edges ``lo`` / ``hi`` (the means
+    only where the bin is not empty), and ``under`` / ``over`` for keys below ``lo`` and at or above ``hi``
+    (or NaN).  A mean over values that include a non-finite one is NaN."""
+    nbins = engine._bins(bins)[2] if bins is not None else 1
+    v = engine.blind_value(report, nbins).tolist()
+
+    def entry(row, head):
+        count = int(row[0])
+        e = dict(head, count=count)
+        if count > 0:
+            for i, k in enumerate(BLIND_KEYS):
+                e[k] = row[1 + i] / count
+            e["flagged_fraction"] = row[_lib.BLIND_VALUES - 1] / count
+        return e
+
+    out = entry(v[nbins + 2], {"lags": options[0], "alpha": options[1], "q_crit": options[2]})
     if out["count"] <= 0:
         raise ValueError("no spectra were evaluated")
     if bins is not None:
@@ -175,33 +222,40 @@ def _workspace(model, n, L, device):
 
 
 class _Meters:
-    """One model's exact accumulator and its optional SNR and PhysicsAwareLoss reports: the forward +
+    """One model's exact accumulator and its optional SNR, PhysicsAwareLoss and blind reports: the forward +
     metrics of each batch go into ``acc`` (``per_spectrum``: the SNR report wants their per-spectrum
     output), add() runs the batch's report passes, summary() all-reduces and summarises."""
 
-    def __init__(self, device, snr_bins, weights):
-        self.snr_bins, self.weights = snr_bins, weights
+    def __init__(self, device, snr_bins, weights, blind=None):
+        self.snr_bins, self.weights, self.blind = snr_bins, weights, blind
         self.phys_bins = snr_bins if snr_bins is not None else (0.0, 1.0, 1)      # unbinned: one bin, no key
         self.acc = engine.new_acc(device)
         self.report = engine.new_report(engine._bins(snr_bins)[2], device) if snr_bins is not None else None
         self.phys_rep = (engine.new_physics_report(engine._bins(self.phys_bins)[2], device)
                          if weights is not None else None)
+        self.blind_rep = (engine.new_blind_report(engine._bins(self.phys_bins)[2], device)
+                          if blind is not None else None)
         self.per_spectrum = self.report is not None
 
     def add(self, x, y, clean, per, key):
-        """The SNR pass, then the physics pass, of a batch (``per``: its per-spectrum metrics; ``key``: its
-        nominal SNRs or None, which bins by the measured SNR_in)."""
+        """The SNR pass, then the physics pass, then the blind pass, of a batch (``per``: its per-spectrum
+        metrics; ``key``: its nominal SNRs or None, which bins by the measured SNR_in)."""
         if self.report is None:
             key = None
         else:
-            # without nominal SNRs the physics report needs the key rdn_snr bins by: its SNR_in in fp32
+            # without nominal SNRs the physics and blind reports need the key rdn_snr bins by: its SNR_in in fp32
+            keyed = self.phys_rep is not None or self.blind_rep is not None
             per3, _ = engine.snr(x, y, clean, key=key, bins=self.snr_bins, per4=per, report=self.report,
-                                 per_spectrum=self.phys_rep is not None and key is None)
+                                 per_spectrum=keyed and key is None)
             if per3 is not None:
                 key = per3[:, 0].to(torch.float32).contiguous()
         if self.phys_rep is not None:
             engine.physics(x, y, clean, weights=self.weights, key=key, bins=self.phys_bins, report=self.phys_rep,
                            per_spectrum=False)
+        if self.blind_rep is not None:
+            # unbinned (no snr_bins): the one-bin report's rows split by SNR_est, only their total is read
+            engine.blind(x, y, lags=self.blind[0], q_crit=self.blind[2], key=key, bins=self.phys_bins,
+                         report=self.blind_rep, per_spectrum=False)
 
     def summary(self, L, words=False):
         """All-reduce the accumulator and the reports: (means, what snr_bins / physics add to a result --
@@ -216,10 +270,15 @@ class _Meters:
             extra["physics"] = physics_summary(_all_reduce_acc(self.phys_rep), self.weights, L, self.snr_bins)
             if words:
                 extra["physics"]["report"] = self.phys_rep.cpu().tolist()
+        if self.blind_rep is not None:
+            extra["blind"] = blind_summary(_all_reduce_acc(self.blind_rep), self.blind, self.snr_bins)
+            if words:
+                extra["blind"]["report"] = self.blind_rep.cpu().tolist()
         return means, extra
 
 
-def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bins=None, snrs=None, physics=None):
+def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bins=None, snrs=None, physics=None,
+             blind=None):
     """evaulate.py:25-39 batched on the device.  Inputs beyond the 16-bit modes' domain (|x| > 4) or
     activations beyond the e4m3 planes' range raise RangeError after the run (one check at the end,
     no per-batch wait) -- unlike the module's own forward, which re-runs such a batch in fp32: evaluate
@@ -233,7 +292,12 @@ def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bi
     ``physics`` = True (the reference's weights 0.1, 0.05, 0.01) or (alpha, beta, gamma) additionally runs
     the PhysicsAwareLoss pass on every batch (engine.physics) and adds one key, ``"physics"``
     (physics_summary): the terms PIDN / APIDN were trained against, their weighted total and -- with
-    ``snr_bins`` -- the same per bin of the key the SNR report bins by."""
+    ``snr_bins`` -- the same per bin of the key the SNR report bins by.
+
+    ``blind`` = True (16 lags, alpha = 0.01) or {"lags": ..., "alpha": ...} additionally runs the blind
+    residual pass on every batch (engine.blind with its own noise estimate) and adds one key, ``"blind"``
+    (blind_summary), binned like the physics entry: the numbers evaluate_blind gives without ``clean``,
+    here beside the true SNR gain that calibrates them."""
     model.eval()
     if device is None:
         device = _module_device(model)
@@ -247,7 +311,7 @@ def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bi
     if device.type != "cuda":
         raise RuntimeError("raman_mi355x.evaluate runs its metrics on the GPU; on a CPU device use the module "
                            "itself in the reference's evaulate.py loop (its forward falls back to eager PyTorch)")
-    m = _Meters(device, snr_bins, _physics_weights(physics))
+    m = _Meters(device, snr_bins, _physics_weights(physics), _blind_options(blind))
     if snrs is not None:
         if snr_bins is None:
             raise ValueError("snrs is the binning key of the SNR report: pass snr_bins=(lo, hi, nbins)")
@@ -279,7 +343,7 @@ def evaluate(model, noisy_data, clean_data, batch_size=1024, device=None, snr_bi
 
 def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_size=8192, device=None,
                        first_index=0, gen_kwargs=None, log_every_s=0.0, fused_metrics=True, snr_bins=None,
-                       physics=None):
+                       physics=None, blind=None):
     """Config 4: ``total`` simulator spectra [first_index, first_index + total),
     sharded over the ranks as [r·N/W, (r+1)·N/W), each chunk generated on the device, denoised by
     every model in ``models`` (name -> module) and metered into that model's exact accumulator.  A module
@@ -297,12 +361,16 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
     size or batch size, like the means.
     ``physics`` = True or (alpha, beta, gamma) additionally runs the PhysicsAwareLoss pass on every chunk
     (binned by the nominal SNR when ``snr_bins`` is given) and adds ``"physics"`` (physics_summary, with
-    the all-reduced ``report`` words) to each model's entry -- exact accumulators, the same bits likewise."""
+    the all-reduced ``report`` words) to each model's entry -- exact accumulators, the same bits likewise.
+    ``blind`` = True or {"lags": ..., "alpha": ...} additionally runs the blind residual pass on every chunk
+    (binned by the nominal SNR when ``snr_bins`` is given) and adds ``"blind"`` (blind_summary, with the
+    all-reduced ``report`` words) to each model's entry, likewise."""
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
     gen_kwargs = gen_kwargs or {}
     weights = _physics_weights(physics)
+    blind = _blind_options(blind)
     rank, W = world()
     lo, hi = shard(total, rank, W)
     L = int(signal_length)
@@ -314,7 +382,7 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
     with torch.no_grad():
         for name, model in models.items():
             model.eval()
-            m = _Meters(device, snr_bins, weights)
+            m = _Meters(device, snr_bins, weights, blind)
             ws = _workspace(model, B, L, device)
             eng = _engine_module(model)          # any other module (baselines.py) runs its own forward
             packed = model.packed_weights(device) if eng else None
@@ -362,6 +430,41 @@ def evaluate_synthetic(models, total, seed=20250410, signal_length=10000, batch_
             out[name] = {"means": means, "acc": m.acc.cpu().tolist(), "spectra": int(total),
                          "seconds": el, "spectra_per_s": total / el if el > 0 else None, **extra}
     return out
+
+
+def evaluate_blind(model, noisy_data, batch_size=1024, device=None, lags=16, alpha=0.01, bins=None, sigma=None):
+    """What can be said about ``model``'s output on spectra that have no clean reference (measured traces):
+    the residual analysis of engine.blind over ``noisy_data`` (N, L) or (N, 1, L), in batches on the device.
+    Returns blind_summary's entry: ``lags``, ``alpha``, ``q_crit`` = blind_q_crit(lags, alpha), ``count``, the
+    means of Mean, RMS, Ratio, Rho1, RhoMax, Q and SNR_est and ``flagged_fraction``; with ``bins`` = (lo, hi,
+    nbins) also ``by_snr`` / ``under`` / ``over``, the same per bin of the estimated input SNR (SNR_est, dB).
+    ``sigma``: None, each spectrum's own blind estimate (noise_mad(x) sqrt(2) / 0.6745); a float for all
+    spectra; or N values, one per spectrum.  Under torch.distributed each rank evaluates its shard and the
+    report is all-reduced: exact accumulators, the same bits for any batch size or world size."""
+    model.eval()
+    if device is None:
+        device = _module_device(model)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("raman_mi355x.evaluate_blind runs its residual analysis on the GPU")
+    options = _blind_options({"lags": lags, "alpha": alpha})
+    noisy = _as_rows(noisy_data)
+    lo, hi = shard(noisy.shape[0])
+    if sigma is not None and not isinstance(sigma, (int, float)):
+        sigma = torch.as_tensor(np.asarray(sigma.cpu() if torch.is_tensor(sigma) else sigma), dtype=torch.float64).reshape(-1)
+        if sigma.numel() != noisy.shape[0]:
+            raise ValueError(f"sigma has {sigma.numel()} values for {noisy.shape[0]} spectra")
+    rep_bins = bins if bins is not None else (0.0, 1.0, 1)      # unbinned: only the totals are read
+    report = engine.new_blind_report(engine._bins(rep_bins)[2], device)
+    with torch.no_grad():
+        for b0 in range(lo, hi, batch_size):
+            b1 = min(hi, b0 + batch_size)
+            x = torch.as_tensor(noisy[b0:b1], dtype=torch.float32).to(device).unsqueeze(1).contiguous()
+            y = model(x)
+            s = sigma[b0:b1].to(device) if torch.is_tensor(sigma) else sigma
+            engine.blind(x, y.contiguous(), sigma=s, lags=options[0], q_crit=options[2], bins=rep_bins, report=report,
+                         per_spectrum=False)
+    return blind_summary(_all_reduce_acc(report), options, bins)
 
 
 def write_metrics(metrics, root="eval_results"):
@@ -418,6 +521,28 @@ def write_physics_report(result, root):
     cols = PHYS_KEYS + ("PeakMasked",)
     with open(os.path.join(root, "physics_report.txt"), "w") as f:
         f.write("weights: " + " ".join(f"{w:g}" for w in part["weights"]) + "\n")
+        f.write(f"count: {part['count']}\n")
+        for k in cols:
+            f.write(f"{k}: {part[k]:.6e}\n")
+        if "by_snr" in part:
+            _write_table(f, cols, [part["under"]] + list(part["by_snr"]) + [part["over"]], ".6e")
+    return root
+
+
+def write_blind_report(result, root):
+    """Write an ``evaluate_blind`` result, or the ``"blind"`` entry of an ``evaluate(..., blind=...)`` result,
+    into the directory ``root``: ``blind_report.json`` (the entry as it is) and ``blind_report.txt`` -- the
+    lags, alpha and q_crit, the means and the flagged share, and with bins a table with one line per bin."""
+    import json
+    part = result.get("blind", result)
+    if not isinstance(part, dict) or "flagged_fraction" not in part:
+        raise ValueError("the result has no blind report: use evaluate_blind, or evaluate with blind=True")
+    os.makedirs(root, exist_ok=True)
+    with open(os.path.join(root, "blind_report.json"), "w") as f:
+        json.dump(part, f, indent=1)
+    cols = BLIND_KEYS + ("flagged_fraction",)
+    with open(os.path.join(root, "blind_report.txt"), "w") as f:
+        f.write(f"lags: {part['lags']}\nalpha: {part['alpha']:g}\nq_crit: {part['q_crit']:.6f}\n")
         f.write(f"count: {part['count']}\n")
         for k in cols:
             f.write(f"{k}: {part[k]:.6e}\n")

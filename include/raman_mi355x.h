@@ -523,6 +523,66 @@ int rdn_noise_mad(const float* x, double* med, int64_t n, int64_t L, void* strea
 int rdn_potts(const float* x, float* y, int32_t* nseg /* may be NULL */, const double* gamma /* DEVICE [n] */,
               int64_t n, int64_t L, int max_len, uint8_t* work, size_t work_bytes, void* stream);
 
+/* ---- blind residual report (added to ABI v6 without a version bump: detect the entry points by symbol) ----
+ *
+ * What can be said about a denoised spectrum without its clean twin (a measured trace has none): if y is the
+ * signal, r = x - y is the noise -- its RMS is the noise level, its mean is zero and it is white.  A denoiser
+ * that removes signal leaves autocorrelation in r and a Ljung-Box Q far above its K degrees of freedom; one
+ * that under-smooths leaves an RMS below the noise estimate.  x: the noisy input, y: the denoised output,
+ * fp32 [n][L] device; sigma: fp64 [n] DEVICE, each spectrum's noise level (e.g. rdn_noise_mad's m times
+ * sqrt(2) / 0.6744897501960817); K = lags, 1 <= K <= RDN_BLIND_MAX_LAGS, K < L < 2^31.  Per spectrum, all
+ * arithmetic is fp64 on the stored fp32 values, each operation rounded on its own, none fused:
+ *   a_i = (double)x_i;  b_i = (double)y_i;  r_i = a_i - b_i
+ *   Mean = (sum_i r_i) / L          RMS = sqrt((sum_i r_i^2) / L)          Ratio = RMS / sigma
+ *   d_i = r_i - Mean                D = sum_i d_i^2                         (two passes: centred after the mean)
+ *   rho_k = (sum_{i < L-k} d_i * d_{i+k}) / D,   k = 1..K                   Rho1 = rho_1
+ *   RhoMax = NaN if any rho_k is NaN, else max_k |rho_k|
+ *   Q = ((double)L * (double)(L+2)) * sum_{k=1..K, ascending} (rho_k * rho_k) / (double)(L - k)    (Ljung-Box)
+ *   S = (sum_i a_i^2) / L;  s2 = sigma * sigma;  SNR_est = 10 * log10((S - s2) / s2)                [dB]
+ *   flagged = Q > q_crit            (false for a NaN Q)
+ * The sums over i are taken in an order the code fixes (no floating-point atomics).  A spectrum's seven values
+ * and its rho row depend on its own samples, its own sigma and K only: not on n, its row index or the launches
+ * a huge n is split into.  Zero denominators, NaN or infinite samples and a NaN, zero or negative sigma give
+ * the IEEE result, written as it is and counted in the out-of-range word of that quantity in a report: nothing
+ * is clamped or skipped (the contract of rdn_snr).
+ *
+ * per_spectrum7: fp64 [n][7] device {Mean, RMS, Ratio, Rho1, RhoMax, Q, SNR_est}, or NULL.  rho: fp64
+ * [n][lags] device {rho_1 .. rho_K}, or NULL.  report: device, RDN_BLIND_WORDS(nbins) int64, ACCUMULATED (integer
+ * atomics only), or NULL: RDN_REPORT_ROWS(nbins) = nbins + 2 rows of RDN_BLIND_ROW_WORDS words with the row
+ * structure of the SNR report (row 0 underflow, rows 1 .. nbins the uniform bins of [lo, hi), row nbins + 1
+ * overflow / NaN key).  A row holds RDN_BLIND_QUANTITIES exact accumulators of RDN_ACC_STRIDE words in the
+ * order above, in rdn_metrics_ex's limb format, then word RDN_BLIND_COUNT, the number of spectra in the row,
+ * then word RDN_BLIND_FLAGGED, the number of those that were flagged.  The bin of a spectrum is that of
+ * key[n], or of (float)SNR_est when key is NULL, by the SAME bin formula as rdn_snr (above; rdn_report_bin
+ * evaluates it on the host).  Integer sums: the same bits for any batch split, atomics order or number of ranks.
+ *
+ * RDN_EINVAL, checked before any device call and also for n = 0: a NULL sigma; lags outside
+ * [1, RDN_BLIND_MAX_LAGS]; L <= lags or L >= 2^31; n < 0; a NaN or negative q_crit (+inf is allowed and flags
+ * nothing); none of per_spectrum7, rho and report given; with a report, nbins outside
+ * [1, RDN_REPORT_MAX_BINS] or lo / hi not finite with lo < hi; without a report, a non-NULL key; for n > 0 a
+ * NULL x or y, or any output overlapping an input or another output.  n = 0 launches nothing.  The library
+ * keeps no device state and never synchronises; the call is asynchronous on `stream`. */
+#define RDN_BLIND_MAX_LAGS 32
+#define RDN_BLIND_QUANTITIES 7
+#define RDN_BLIND_COUNT (RDN_BLIND_QUANTITIES * RDN_ACC_STRIDE)
+#define RDN_BLIND_FLAGGED (RDN_BLIND_COUNT + 1)
+#define RDN_BLIND_ROW_WORDS (RDN_BLIND_FLAGGED + 1)
+#define RDN_BLIND_WORDS(nbins) (RDN_REPORT_ROWS(nbins) * RDN_BLIND_ROW_WORDS)
+/* doubles per row of rdn_blind_value: {count, sum Mean, RMS, Ratio, Rho1, RhoMax, Q, SNR_est, flagged} */
+#define RDN_BLIND_VALUES (RDN_BLIND_QUANTITIES + 2)
+#define RDN_BLIND_LDS_L 20000        /* the longest spectrum whose residual is staged in LDS; longer ones are
+                                        recomputed from x and y through L2 (tests probe the sizes around it) */
+int rdn_blind(const float* x, const float* y, const double* sigma /* DEVICE [n] */, int64_t n, int64_t L,
+              int lags, double q_crit, double* per_spectrum7 /* [n][7] or NULL */, double* rho /* [n][lags] or NULL */,
+              const float* key /* [n] or NULL */, float lo, float hi, int nbins, int64_t* report /* or NULL */,
+              void* stream);
+
+/* Host: doubles of a HOST copy of a report of rdn_blind.  out: (RDN_REPORT_ROWS(nbins) + 1) rows of
+ * RDN_BLIND_VALUES doubles: the report's rows in order, then the totals over all rows (their limbs added as
+ * integers).  Each sum is the exact accumulated value rounded once to the nearest double, NaN for a
+ * quantity with an out-of-range value in that row (the contract of rdn_acc_value). */
+int rdn_blind_value(const int64_t* report, int nbins, double* out);
+
 #ifdef __cplusplus
 }
 #endif
