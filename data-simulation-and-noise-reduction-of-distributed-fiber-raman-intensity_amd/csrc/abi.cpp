@@ -17,6 +17,7 @@
 #include "filters.hpp"
 #include "haar.hpp"
 #include "potts.hpp"
+#include "bayes.hpp"
 #include "blind.hpp"
 
 namespace rdn {
@@ -681,6 +682,43 @@ int rdn_potts(const float* x, float* y, int32_t* nseg, const double* gamma, int6
                rdn::overlaps(nseg, sbytes, work, work_bytes)))
     return fail(RDN_EINVAL, fn + ": nseg overlaps x, y or work");
   return hip_check(rdn::launch_potts(x, y, nseg, gamma, n, (int)L, max_len, work, (hipStream_t)stream), "potts");
+  RDN_GUARD_END
+}
+
+int rdn_bayes_steps(const float* x, float* y, float* jump, double* logz, const double* sigma, int64_t n, int64_t L,
+                    int max_len, double level_range, double* work, size_t work_bytes, void* stream) {
+  RDN_GUARD_BEGIN
+  const std::string fn = "rdn_bayes_steps";
+  if (!sigma) return fail(RDN_EINVAL, fn + ": null sigma");
+  if (n < 0) return fail(RDN_EINVAL, fn + ": need n >= 0");
+  if (max_len < 1 || max_len > RDN_BAYES_MAX_LEN)
+    return fail(RDN_EINVAL, fn + ": need 1 <= max_len <= " + std::to_string(RDN_BAYES_MAX_LEN));
+  if (!std::isfinite(level_range) || level_range <= 0.0)
+    return fail(RDN_EINVAL, fn + ": level_range must be finite and > 0");
+  if (bad_rows(0, L, 1)) return fail(RDN_EINVAL, fn + ": need 1 <= L < 2^31");
+  if (n == 0) return RDN_OK;
+  if (!(x && y && work)) return fail(RDN_EINVAL, fn + ": null pointer");
+  if ((uintptr_t)work % sizeof(double)) return fail(RDN_EINVAL, fn + ": work is not 8-byte aligned");
+  if ((uint64_t)n > (uint64_t)SIZE_MAX / ((uint64_t)L + 1) / sizeof(double) ||
+      work_bytes < (size_t)n * ((size_t)L + 1) * sizeof(double))
+    return fail(RDN_EINVAL, fn + ": work_bytes is below n * (L + 1) * 8");
+  const size_t bytes = row_bytes(n, L), zbytes = (size_t)n * sizeof(double);
+  if (rdn::overlaps(x, bytes, y, bytes)) return fail(RDN_EINVAL, fn + ": x and y overlap");
+  // G lands in work while x is still to be read, and is read while y and jump are written
+  if (rdn::overlaps(work, work_bytes, x, bytes) || rdn::overlaps(work, work_bytes, y, bytes))
+    return fail(RDN_EINVAL, fn + ": work overlaps x or y");
+  if (jump && (rdn::overlaps(jump, bytes, x, bytes) || rdn::overlaps(jump, bytes, y, bytes) ||
+               rdn::overlaps(jump, bytes, work, work_bytes)))
+    return fail(RDN_EINVAL, fn + ": jump overlaps x, y or work");
+  if (logz && (rdn::overlaps(logz, zbytes, x, bytes) || rdn::overlaps(logz, zbytes, y, bytes) ||
+               rdn::overlaps(logz, zbytes, work, work_bytes) || (jump && rdn::overlaps(logz, zbytes, jump, bytes))))
+    return fail(RDN_EINVAL, fn + ": logz overlaps x, y, work or jump");
+  // a spectrum's sigma is read when its wave starts: after other spectra's outputs have landed
+  if (rdn::overlaps(sigma, zbytes, y, bytes) || rdn::overlaps(sigma, zbytes, work, work_bytes) ||
+      (jump && rdn::overlaps(sigma, zbytes, jump, bytes)) || (logz && rdn::overlaps(sigma, zbytes, logz, zbytes)))
+    return fail(RDN_EINVAL, fn + ": sigma overlaps y, work, jump or logz");
+  return hip_check(rdn::launch_bayes_steps(x, y, jump, logz, sigma, n, (int)L, max_len, level_range, work,
+                                           (hipStream_t)stream), "bayes_steps");
   RDN_GUARD_END
 }
 

@@ -12,8 +12,8 @@
 // host side of the SNR report (rdn_snr's argument checks, rdn_report_bin, rdn_report_value on an
 // exactly-sized report) and of the PhysicsAwareLoss report (rdn_physics's argument checks,
 // rdn_physics_value); and the argument checks of the baseline filters (rdn_fir, rdn_median), of
-// rdn_haar_shrink, of rdn_physics_grad, and of rdn_potts and rdn_noise_mad (every refusal, each overlap pair,
-// n = 0 succeeding).
+// rdn_haar_shrink, of rdn_physics_grad, of rdn_potts and rdn_noise_mad, and of rdn_bayes_steps (every refusal, each
+// overlap pair, n = 0 succeeding).
 // And the pure host helpers of the launch path, which no device test can reach: the once-per-(kernel,
 // device) bookkeeping of the LDS opt-in with a counting fake setter (host_util.hpp once_per: repeats,
 // device bounds, a failing setter, 8 racing threads, a full table), the chunk walk (for_chunks,
@@ -24,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <thread>
 #include <vector>
@@ -275,6 +276,62 @@ static void check_potts_and_mad_args() {
   }
 }
 
+// rdn_bayes_steps: likewise every refusal, each overlap pair, n = 0 succeeding
+static void check_bayes_args() {
+  std::vector<double> buf(256, 0.0);
+  float* b = (float*)buf.data();
+  // n = 1, L = 16: x at floats 0 .. 15, y at 16 .. 31, jump at 32 .. 47, work (17 doubles) at float 64 .. 97,
+  // logz at float 128, sigma at float 160
+  double* const w = (double*)(b + 64);
+  double* const z = (double*)(b + 128);
+  const double* const s = (const double*)(b + 160);
+  const size_t wb = 17 * sizeof(double);
+  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  const auto bayes = [&](const float* x, float* y, float* jump, double* logz, const double* sigma, int64_t n, int64_t L,
+                         int K, double W, double* work, size_t bytes) {
+    return rdn_bayes_steps(x, y, jump, logz, sigma, n, L, K, W, work, bytes, nullptr);
+  };
+  EXPECT(refused(bayes(b, b + 16, b + 32, z, nullptr, 1, 16, 40, 1.0, w, wb), "null sigma"));
+  EXPECT(refused(bayes(nullptr, nullptr, nullptr, nullptr, nullptr, 0, 16, 40, 1.0, nullptr, 0), "null sigma"));
+  EXPECT(refused(bayes(b, b + 16, b + 32, z, s, -1, 16, 40, 1.0, w, wb), "need n >= 0"));
+  for (int K : {0, -1, RDN_BAYES_MAX_LEN + 1}) {
+    EXPECT(refused(bayes(b, b + 16, b + 32, z, s, 1, 16, K, 1.0, w, wb), "max_len"));
+    EXPECT(refused(bayes(nullptr, nullptr, nullptr, nullptr, s, 0, 16, K, 1.0, nullptr, 0), "max_len"));
+  }
+  for (double W : {0.0, -1.0, nan, inf, -inf}) {
+    EXPECT(refused(bayes(b, b + 16, b + 32, z, s, 1, 16, 40, W, w, wb), "level_range"));
+    EXPECT(refused(bayes(nullptr, nullptr, nullptr, nullptr, s, 0, 16, 40, W, nullptr, 0), "level_range"));
+  }
+  for (int64_t L : {(int64_t)0, (int64_t)-3, (int64_t)1 << 31}) {
+    EXPECT(refused(bayes(b, b + 16, b + 32, z, s, 1, L, 40, 1.0, w, (size_t)1 << 40), "1 <= L < 2^31"));
+    EXPECT(refused(bayes(nullptr, nullptr, nullptr, nullptr, s, 0, L, 40, 1.0, nullptr, 0), "1 <= L < 2^31"));
+  }
+  EXPECT(refused(bayes(nullptr, b + 16, b + 32, z, s, 1, 16, 40, 1.0, w, wb), "null pointer"));
+  EXPECT(refused(bayes(b, nullptr, b + 32, z, s, 1, 16, 40, 1.0, w, wb), "null pointer"));
+  EXPECT(refused(bayes(b, b + 16, b + 32, z, s, 1, 16, 40, 1.0, nullptr, wb), "null pointer"));
+  EXPECT(refused(bayes(b, b + 16, b + 32, z, s, 1, 16, 40, 1.0, (double*)(b + 65), wb), "8-byte aligned"));
+  EXPECT(refused(bayes(b, b + 16, b + 32, z, s, 1, 16, 40, 1.0, w, wb - 1), "work_bytes"));
+  EXPECT(refused(bayes(b, b + 16, b + 32, z, s, 2, 7, 40, 1.0, w, 127), "work_bytes"));
+  EXPECT(refused(bayes(b, b + 15, b + 32, z, s, 1, 16, 40, 1.0, w, wb), "x and y overlap"));
+  EXPECT(refused(bayes(b + 15, b, b + 32, z, s, 1, 16, 40, 1.0, w, wb), "x and y overlap"));
+  EXPECT(refused(bayes(b, b + 16, b + 48, z, s, 1, 16, 40, 1.0, (double*)(b + 14), wb), "work overlaps"));     // x's last 8 bytes
+  EXPECT(refused(bayes(b + 200, b + 32, nullptr, z, s, 1, 16, 40, 1.0, (double*)b, wb), "work overlaps"));     // y's first 8
+  EXPECT(refused(bayes(b, b + 16, b + 15, z, s, 1, 16, 40, 1.0, w, wb), "jump overlaps"));                     // x and y
+  EXPECT(refused(bayes(b, b + 16, b + 31, z, s, 1, 16, 40, 1.0, w, wb), "jump overlaps"));                     // y's last sample
+  EXPECT(refused(bayes(b, b + 16, b + 97, z, s, 1, 16, 40, 1.0, w, wb), "jump overlaps"));                     // work's last 4 bytes
+  EXPECT(refused(bayes(b, b + 16, b + 32, (double*)(b + 14), s, 1, 16, 40, 1.0, w, wb), "logz overlaps"));     // x
+  EXPECT(refused(bayes(b, b + 16, b + 32, (double*)(b + 30), s, 1, 16, 40, 1.0, w, wb), "logz overlaps"));     // y
+  EXPECT(refused(bayes(b, b + 16, b + 32, (double*)(b + 96), s, 1, 16, 40, 1.0, w, wb), "logz overlaps"));     // work's last double
+  EXPECT(refused(bayes(b, b + 16, b + 32, (double*)(b + 46), s, 1, 16, 40, 1.0, w, wb), "logz overlaps"));     // jump
+  EXPECT(refused(bayes(b, b + 16, b + 32, z, s, 1, 16, 40, 1.0, w, 33 * sizeof(double)), "logz overlaps"));    // the stated extent
+  EXPECT(refused(bayes(b, b + 16, b + 32, z, (const double*)(b + 30), 1, 16, 40, 1.0, w, wb), "sigma overlaps"));   // y
+  EXPECT(refused(bayes(b, b + 16, b + 32, z, (const double*)(b + 46), 1, 16, 40, 1.0, w, wb), "sigma overlaps"));   // jump
+  EXPECT(refused(bayes(b, b + 16, b + 32, z, w + 16, 1, 16, 40, 1.0, w, wb), "sigma overlaps"));               // work
+  EXPECT(refused(bayes(b, b + 16, b + 32, z, z, 1, 16, 40, 1.0, w, wb), "sigma overlaps"));                    // logz
+  EXPECT(bayes(nullptr, nullptr, nullptr, nullptr, s, 0, 16, 40, 1.0, nullptr, 0) == RDN_OK);
+  EXPECT(bayes(nullptr, nullptr, nullptr, nullptr, s, 0, ((int64_t)1 << 31) - 1, 1, 2.5, nullptr, 0) == RDN_OK);
+}
+
 int main(int argc, char** argv) {
   if (argc != 5) {
     std::fprintf(stderr, "usage: host_check <arch> <dtype> <tensors.bin> <blob_out.bin>\n");
@@ -460,6 +517,7 @@ int main(int argc, char** argv) {
 
   check_haar_and_grad_args();
   check_potts_and_mad_args();
+  check_bayes_args();
   check_once_per();
   check_chunks();
   check_overlaps();

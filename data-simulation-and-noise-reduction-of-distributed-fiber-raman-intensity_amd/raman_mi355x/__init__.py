@@ -18,8 +18,12 @@ Drop-in surfaces (reference file:line):
                                                   (engine.blind; no reference counterpart)
   PottsFit                                        the exact piecewise-constant (jump-penalised least-squares) fit with the same
                                                   noise estimate (potts.py, engine.potts; no reference counterpart)
+  BayesSteps                                      the posterior mean under the simulator's own signal model, the jump
+                                                  probability of every sample and the log evidence (bayes.py,
+                                                  engine.bayes_steps; no reference counterpart)
 """
 from . import engine
+from .bayes import BayesSteps
 from .baselines import (BASELINES, GaussianSmooth, MedianFilter, MovingAverage, SavitzkyGolay, gaussian_taps,
                         savgol_taps)
 from ._lib import EngineError, RangeError
@@ -37,5 +41,5 @@ __all__ = ["engine", "DenoiseCNN", "RRCDNet", "DSDN", "ADSDN", "PIDN", "APIDN", 
            "generate_signals", "evaluate", "write_metrics", "write_snr_report", "load_dataset", "save_dataset", "shard",
            "all_reduce_sums", "EngineError", "RangeError", "PhysicsAwareLoss", "write_physics_report", "evaluate_synthetic",
            "write_comparison", "BASELINES", "MovingAverage", "SavitzkyGolay", "GaussianSmooth", "MedianFilter", "savgol_taps",
-           "gaussian_taps", "HaarShrink", "haar_thresholds", "PottsFit", "evaluate_blind", "blind_q_crit",
+           "gaussian_taps", "HaarShrink", "haar_thresholds", "PottsFit", "BayesSteps", "evaluate_blind", "blind_q_crit",
            "write_blind_report"]

@@ -63,6 +63,8 @@ HAAR_SELECT_LDS_L = 12288
 HAAR_SOFT, HAAR_HARD = 0, 1
 # exact piecewise-constant (Potts) fit (include/raman_mi355x.h RDN_POTTS_*)
 POTTS_MAX_LEN = 64
+# Bayesian change-point smoother (include/raman_mi355x.h RDN_BAYES_*)
+BAYES_MAX_LEN = 64
 # blind residual report (include/raman_mi355x.h RDN_BLIND_*)
 BLIND_MAX_LAGS = 32
 BLIND_QUANTITIES = 7
@@ -162,6 +164,10 @@ _SIGNATURES = {
     "rdn_noise_mad": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
     "rdn_potts": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                    ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
+    # the Bayesian change-point smoother: likewise
+    "rdn_bayes_steps": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                         ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
+                         ctypes.c_size_t, ctypes.c_void_p], ctypes.c_int),
     # the blind residual report: likewise added to ABI v6 and detected by symbol
     "rdn_blind": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                    ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_float,

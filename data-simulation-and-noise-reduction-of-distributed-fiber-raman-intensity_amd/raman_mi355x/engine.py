@@ -859,6 +859,68 @@ def potts(x, gamma, max_len=POTTS_MAX_LEN, out=None, nseg=None, work=None):
     return y, segs
 
 
+# ---- Bayesian change-point smoother (rdn_bayes_steps; the arithmetic contract: include/raman_mi355x.h) ----
+BAYES_MAX_LEN = _lib.BAYES_MAX_LEN              # the longest run: one candidate per lane of a wave
+
+
+def bayes_steps(x, sigma, max_len=40, level_range=1.0, out=None, jump=None, logz=None, work=None):
+    """The posterior mean of every spectrum of ``x`` (float32 (N, L) or (N, 1, L), contiguous, CUDA) under the
+    simulator's signal model -- runs of 1 to ``max_len`` (at most 64) equal samples, levels uniform on a range of
+    width ``level_range``, white Gaussian noise of standard deviation ``sigma`` -- by an exact forward-backward
+    recursion in fp64, rounded once to fp32 (rdn_bayes_steps).  ``sigma``: a float64 CUDA tensor (N,), one per
+    spectrum, or a Python float for all of them.  Returns (y, jump, logz): y float32 of x's shape; jump float32 of
+    x's shape, the posterior probability that a run starts at each sample (1 at the first); logz float64 (N,),
+    the log evidence.  A spectrum with a NaN or an infinity, or with a NaN, infinite, zero or negative sigma,
+    gives NaN in all three.  ``out`` / ``jump`` / ``logz``: buffers to write into; ``work``: float64 scratch of at
+    least N · (L + 1) elements (each made when None).  None of them may overlap another, x or sigma."""
+    _check_rows_input(x)
+    if isinstance(max_len, bool) or int(max_len) != max_len or not 1 <= int(max_len) <= BAYES_MAX_LEN:
+        raise ValueError(f"max_len must be an integer in [1, {BAYES_MAX_LEN}], got {max_len!r}")
+    if isinstance(level_range, bool) or not 0.0 < float(level_range) < float("inf"):
+        raise ValueError(f"level_range must be positive and finite, got {level_range!r}")
+    n, L = x.shape[0], x.shape[-1]
+    if L < 1:
+        raise ValueError("spectra must have at least one sample")
+    if torch.is_tensor(sigma):
+        _check_out(sigma, "sigma", (n,), x.device, torch.float64)
+    else:
+        if isinstance(sigma, bool):
+            raise TypeError(f"sigma must be a float64 tensor or a float, got {sigma!r}")
+        sigma = torch.full((n,), float(sigma), dtype=torch.float64, device=x.device)
+    y = _out_like(x, out)
+    jmp = torch.empty_like(x) if jump is None else jump
+    if jump is not None:
+        _check_out(jmp, "jump", tuple(x.shape), x.device, torch.float32)
+    lz = torch.empty(n, dtype=torch.float64, device=x.device) if logz is None else logz
+    if logz is not None:
+        _check_out(lz, "logz", (n,), x.device, torch.float64)
+    if work is None:
+        work = torch.empty(n * (L + 1), dtype=torch.float64, device=x.device)
+    else:
+        if not torch.is_tensor(work):
+            raise TypeError("work must be a tensor")
+        if work.dtype != torch.float64:
+            raise TypeError(f"work must be torch.float64, got {work.dtype}")
+        if not work.is_cuda or work.device != x.device:
+            raise ValueError(f"work must live on {x.device}, got {work.device}")
+        if not work.is_contiguous():
+            raise ValueError("work must be contiguous")
+        if work.numel() < n * (L + 1):
+            raise ValueError(f"work must have at least N * (L + 1) = {n * (L + 1)} elements, got {work.numel()}")
+    named = ((x, "the input"), (y, "out"), (work, "work"), (jmp, "jump"), (lz, "logz"))
+    for i in range(2, len(named)):               # out against the input: _out_like
+        for b, bn in named[:i]:
+            _no_overlap(named[i][0], b, f"{named[i][1]} must not overlap {bn}")
+    for b, bn in named[1:]:                      # sigma is only read: it may share bytes with the input alone
+        _no_overlap(sigma, b, f"sigma must not overlap {bn}")
+    if n == 0:                                   # nothing to launch (an empty sigma has no address to pass)
+        return y, jmp, lz
+    _lib.check(_lib.lib().rdn_bayes_steps(_ptr(x), _ptr(y), _ptr(jmp), _ptr(lz), _ptr(sigma), n, L, int(max_len),
+                                          float(level_range), _ptr(work), work.numel() * 8, _stream(x.device)),
+               "rdn_bayes_steps")
+    return y, jmp, lz
+
+
 # ---- blind residual report (rdn_blind; definitions and report layout: include/raman_mi355x.h) ----
 BLIND_QUANTITIES = ("Mean", "RMS", "Ratio", "Rho1", "RhoMax", "Q", "SNR_est")
 BLIND_MAX_LAGS = _lib.BLIND_MAX_LAGS

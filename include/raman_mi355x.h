@@ -523,6 +523,50 @@ int rdn_noise_mad(const float* x, double* med, int64_t n, int64_t L, void* strea
 int rdn_potts(const float* x, float* y, int32_t* nseg /* may be NULL */, const double* gamma /* DEVICE [n] */,
               int64_t n, int64_t L, int max_len, uint8_t* work, size_t work_bytes, void* stream);
 
+/* ---- Bayesian change-point smoother (added to ABI v6 without a version bump: detect by symbol) ----
+ *
+ * The posterior mean of each spectrum under the simulator's own signal model -- runs of 1 .. K = max_len equal
+ * samples (the run length uniform), the levels uniform on a range of width W = level_range, white Gaussian
+ * noise of standard deviation sigma -- by an exact forward-backward recursion over the run boundaries; with
+ * it the posterior probability that a run starts at each sample, and the log evidence of the spectrum.
+ * x, y: fp32 [n][L] device, y WRITTEN; jump: fp32 [n][L] device or NULL, WRITTEN; logz: fp64 [n] device or
+ * NULL, WRITTEN; sigma: fp64 [n] DEVICE, one per spectrum; 1 <= K <= RDN_BAYES_MAX_LEN, 1 <= L < 2^31.
+ * Per spectrum, with boundaries 0 .. L (a run [s, t) holds the samples s .. t - 1, n = t - s of them):
+ *   c0 = log((sqrt(2 pi) * sigma) / (W * (double)K));   h = 1.0 / ((2.0 * sigma) * sigma)
+ *   log w(s, t) = (c0 - 0.5 * log((double)n)) - M2(s, t) * h       M2 = sum (x - m)^2 about the run mean m
+ *   G[L] = 0;   G[s] = LSE over n = 1..min(K, L - s) of (G[s + n] + log w(s, s + n)),   s = L - 1 .. 0
+ *   F[0] = 0;   F[t] = LSE over n = 1..min(K, t) of (F[t - n] + log w(t - n, t)),       t = 1 .. L
+ *   logZ = G[0]
+ *   P(s, t) = exp(F[s] + log w(s, t) + G[t] - logZ)              the posterior probability of the run [s, t)
+ *   y[i] = (float)(sum over s <= i < t of P(s, t) * m(s, t))      (one rounding)
+ *   jump[i] = (float)exp(F[i] + G[i] - logZ), i = 1 .. L - 1;     jump[0] = 1.0f exactly
+ * This is the evidence of n samples that share one level under a flat prior of width W, times the run-length
+ * prior 1 / K; the factor common to every segmentation is dropped and every run, the last included, has the
+ * same weight.  All arithmetic is fp64, no operation fused.  m and M2 of a candidate run are Welford sums
+ * started at the run's first sample in the sweep's direction (the right end for G, the left end for F and y):
+ *   d = v - m;  m = m + d * (1.0 / (double)n);  M2 = M2 + d * (v - m)        n the count that includes v
+ * never differences of whole-row prefix sums.  Every LSE is  M + log(sum exp(a - M))  with M the maximum of
+ * its terms.  P(s, t) is formed from the LSE's own terms: exp(a - M) * exp(M + G[t] - logZ), and jump[t] as
+ * (sum exp(a - M)) * exp(M + G[t] - logZ).  The order of each sum is fixed by the code (the 64 candidates of
+ * a step sit in the lanes their boundaries have modulo 64), so a spectrum's output bits depend on its own
+ * samples, its own sigma, K and W only: not on n, its row index or the launches a huge n is split into.
+ * A spectrum that holds a NaN or an infinity, or whose sigma is NaN, infinite or <= 0 (or so small that h is
+ * infinite), gets the quiet NaN 0x7fc00000 at every y and jump and logz = NaN.  fp32 subnormals are read as
+ * their values.
+ *
+ * work: caller-owned device scratch of work_bytes >= n * (L + 1) * 8 bytes, 8-byte aligned, contents
+ * unspecified afterwards (G of every boundary).
+ *
+ * RDN_EINVAL, checked before any device call and also for n = 0: a NULL sigma; n < 0; max_len outside
+ * [1, RDN_BAYES_MAX_LEN]; level_range not finite or <= 0; L < 1 or L >= 2^31; for n > 0 a NULL x, y or work,
+ * a work that is not 8-byte aligned, work_bytes < n * (L + 1) * 8, x and y overlapping, work overlapping x or
+ * y, jump or logz overlapping x, y, work or each other, sigma overlapping anything written.  n = 0 launches nothing and accepts NULL data
+ * pointers.  The library keeps no device state and never synchronises; the call is asynchronous on `stream`. */
+#define RDN_BAYES_MAX_LEN 64
+int rdn_bayes_steps(const float* x, float* y, float* jump /* may be NULL */, double* logz /* may be NULL */,
+                    const double* sigma /* DEVICE [n] */, int64_t n, int64_t L, int max_len, double level_range,
+                    double* work, size_t work_bytes, void* stream);
+
 /* ---- blind residual report (added to ABI v6 without a version bump: detect the entry points by symbol) ----
  *
  * What can be said about a denoised spectrum without its clean twin (a measured trace has none): if y is the

@@ -3,15 +3,18 @@
 
 Part 1 meters the six trained-fixture networks (tests/golden, 'trained' weights, 'f16') and a small grid of
 baseline filters (linear smoothers, running medians, translation-invariant Haar shrinkage, the exact
-piecewise-constant fit) over the same
+piecewise-constant fit, the Bayesian change-point smoother) over the same
 on-device simulator spectra with snr_bins = (20, 37, 17), and writes the table
-to profiles/baselines/comparison.json / comparison.txt (raman_mi355x.write_comparison).
+to profiles/baselines/comparison.json / comparison.txt (raman_mi355x.write_comparison).  The last row,
+true_segmentation, is the ceiling of every piecewise-constant estimate: the run means of the noisy input under the
+clean signal's own runs (plain torch ops on the device; it needs the clean twin, which no denoiser has).
 
 Part 2 times each filter alone at L = 10 000, batch 8192, with HIP events on the launch stream, the filters
 interleaved round by round (round 0 warms up), and writes spectra/s and GB/s (80 KB of HBM traffic per
 spectrum: 40 KB read, 40 KB written) beside the HBM-bound time into profiles/baselines/throughput.json.  The
 piecewise-constant fit is timed as engine.potts alone, with its buffers preallocated and gamma computed before
-the clock starts; its noise estimate is the leg noise_mad.
+the clock starts, and the change-point smoother as engine.bayes_steps alone, likewise; their noise estimate is the
+leg noise_mad.
 
     python tools/baseline_compare.py [--total 8192] [--L 10000] [--batch 2048] [--rounds 12] [--out profiles/baselines]
 """
@@ -30,12 +33,43 @@ HBM_ACHIEVABLE = 6.29e12          # bytes/s, float4 copy on the MI355X (8.0e12 s
 BYTES_PER_SAMPLE = 8              # one fp32 read, one fp32 written
 
 
+def true_segmentation(seed, L):
+    """A module for evaluate_synthetic that returns the run means of its input under the CLEAN signal's own runs.
+    The clean twin of a batch is regenerated from (seed, index of the batch's first spectrum): the module counts
+    the spectra it has seen, and checks that the regenerated noisy batch is the one it was given."""
+    import torch
+    from raman_mi355x import engine
+
+    class TrueSegmentation(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.seen = 0
+
+        def forward(self, x):
+            n = x.shape[0]
+            clean, noisy, _, _ = engine.generate(n, seed, first_index=self.seen, signal_length=L, device=x.device)
+            assert torch.equal(noisy, x.view(n, L)), "the batch is not the simulator's next one"
+            self.seen += n
+            idx = torch.arange(L + 1, device=x.device).expand(n, L + 1)
+            cut = torch.ones((n, L + 1), dtype=torch.bool, device=x.device)      # boundaries 0 .. L
+            cut[:, 1:L] = clean[:, 1:] != clean[:, :-1]
+            start = torch.where(cut, idx, torch.zeros_like(idx))[:, :L].cummax(dim=-1).values
+            end = torch.where(cut, idx, torch.full_like(idx, L + 1))[:, 1:].flip(-1).cummin(dim=-1).values.flip(-1)
+            S = torch.zeros((n, L + 1), dtype=torch.float64, device=x.device)
+            S[:, 1:] = noisy.double().cumsum(dim=-1)
+            mean = (S.gather(1, end) - S.gather(1, start)) / (end - start).double()
+            return mean.float().view(n, 1, L)
+
+    return TrueSegmentation()
+
+
 def baseline_grid():
     from raman_mi355x import baselines as B
+    from raman_mi355x.bayes import BayesSteps
     from raman_mi355x.potts import PottsFit
     from raman_mi355x.wavelets import HaarShrink
     return {"potts8": PottsFit(8.0), "potts10": PottsFit(10.0), "potts12": PottsFit(), "potts16": PottsFit(16.0),
-            "potts_bic": PottsFit("bic"), "haar4_3h": HaarShrink(), "haar3_1.5s": HaarShrink(3, 1.5, "soft"), "haar4_uni_h": HaarShrink(4, "universal"),
+            "potts_bic": PottsFit("bic"), "BayesSteps": BayesSteps(), "haar4_3h": HaarShrink(), "haar3_1.5s": HaarShrink(3, 1.5, "soft"), "haar4_uni_h": HaarShrink(4, "universal"),
             "ma3": B.MovingAverage(3), "ma5": B.MovingAverage(5), "sg5_2": B.SavitzkyGolay(5, 2),
             "sg21_3": B.SavitzkyGolay(21, 3), "gauss1": B.GaussianSmooth(1.0), "gauss2.5": B.GaussianSmooth(2.5),
             "med3": B.MedianFilter(3), "med5": B.MedianFilter(5), "med7": B.MedianFilter(7), "med21": B.MedianFilter(21)}
@@ -63,7 +97,10 @@ def main():
         m.load_state_dict(golden_state_dict(arch, "trained"), strict=True)
         models[arch] = m.to(dev).eval().set_engine_dtype("f16")
     models.update(filters)
-    res = R.evaluate_synthetic(models, a.total, signal_length=a.L, batch_size=a.batch, device=dev, snr_bins=(20, 37, 17))
+    seed = 20250410
+    models["true_segmentation"] = true_segmentation(seed, a.L)
+    res = R.evaluate_synthetic(models, a.total, seed=seed, signal_length=a.L, batch_size=a.batch, device=dev,
+                               snr_bins=(20, 37, 17))
     R.write_comparison(res, a.out)
     print(open(os.path.join(a.out, "comparison.txt")).read(), flush=True)
 
@@ -75,11 +112,17 @@ def main():
     legs = {k: ((lambda m=m: engine.median(x, m.window, out=y)) if isinstance(m, R.MedianFilter) else
                 (lambda m=m: engine.haar_shrink(x, m.factors(L), m.mode, out=y, med=med_buf)) if isinstance(m, R.HaarShrink) else
                 (lambda m=m: engine.fir(x, m.taps, edge_taps=m.edge_taps, out=y))) for k, m in filters.items()
-            if not isinstance(m, R.PottsFit)}
+            if not isinstance(m, (R.PottsFit, R.BayesSteps))}
     gamma = filters["potts12"].gamma(x)                                 # once, outside the timed region
     nseg_buf = torch.empty(n, dtype=torch.int32, device=dev)
     work = torch.empty(n * L, dtype=torch.uint8, device=dev)
     legs["potts12"] = lambda: engine.potts(x, gamma, filters["potts12"].max_len, out=y, nseg=nseg_buf, work=work)
+    bayes = filters["BayesSteps"]
+    sigma = bayes.noise_std(x)                                          # likewise
+    jump_buf, logz_buf = torch.empty_like(x), torch.empty(n, dtype=torch.float64, device=dev)
+    work64 = torch.empty(n * (L + 1), dtype=torch.float64, device=dev)
+    legs["BayesSteps"] = lambda: engine.bayes_steps(x, sigma, bayes.max_len, bayes.level_range, out=y, jump=jump_buf,
+                                                    logz=logz_buf, work=work64)
     legs["noise_mad"] = lambda: engine.noise_mad(x, out=med_buf)
     legs["haar7_3h"] = lambda m=R.HaarShrink(7): engine.haar_shrink(x, m.factors(L), m.mode, out=y, med=med_buf)
     for w in (11, 25, 27, 101):                                         # sorting networks up to 25, then the radix select

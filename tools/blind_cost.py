@@ -8,8 +8,8 @@ Part 1 times, interleaved round by round with HIP events on the launch stream, o
   D  engine.blind with sigma=None: C plus engine.noise_mad and the scaling of its result
 and writes the medians and the ratios C / A, C / B, D / A, D / B to <out>/cost.json.
 
-Part 2 meters the trained-fixture networks (tests/golden, 'trained' weights, 'f16'), MedianFilter(3), HaarShrink
-and PottsFit over the same simulator spectra with evaluate_synthetic(snr_bins=..., blind=True) and writes, per
+Part 2 meters the trained-fixture networks (tests/golden, 'trained' weights, 'f16'), MedianFilter(3), HaarShrink,
+PottsFit and BayesSteps over the same simulator spectra with evaluate_synthetic(snr_bins=..., blind=True) and writes, per
 model, the true SNR_in / SNR_gain beside the blind means and the flagged share to <out>/comparison.txt (and .json).
 
     python tools/blind_cost.py [--batch 8192] [--L 10000] [--rounds 12] [--lags 16] [--total 2048] [--out profiles/blind]
@@ -87,7 +87,8 @@ def comparison(a, dev):
         m = R.MODELS[arch]()
         m.load_state_dict(golden_state_dict(arch, "trained"), strict=True)
         models[arch] = m.to(dev).eval().set_engine_dtype("f16")
-    models.update({"med3": R.MedianFilter(3).to(dev), "haar4_3h": R.HaarShrink().to(dev), "potts12": R.PottsFit().to(dev)})
+    models.update({"med3": R.MedianFilter(3).to(dev), "haar4_3h": R.HaarShrink().to(dev), "potts12": R.PottsFit().to(dev),
+                   "BayesSteps": R.BayesSteps().to(dev)})
     res = R.evaluate_synthetic(models, a.total, signal_length=a.L, batch_size=min(a.total, 1024), device=dev,
                                snr_bins=(20, 37, 17), blind={"lags": a.lags})
     table = {name: dict({k: r[k] for k in TABLE_KEYS[:2]}, **{k: r["blind"][k] for k in TABLE_KEYS[2:]})
