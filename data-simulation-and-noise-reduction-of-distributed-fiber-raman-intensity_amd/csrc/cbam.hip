@@ -1400,8 +1400,12 @@ __device__ __forceinline__ void team_range(const TeamArgs& ta, int team, int nlo
   const int64_t ws = ta.xcd && nloc < ta.teams ? 31 : 32;
   auto cum = [&](int t) -> int64_t { return t <= nloc ? 32LL * t : 32LL * nloc + ws * (t - nloc); };
   const int64_t W = cum(ta.teams);
-  lo = (ta.n * cum(team) + W - 1) / W;         // rounded up: with fewer spectra than teams, team 0
-  hi = (ta.n * cum(team + 1) + W - 1) / W;     // takes spectrum 0
+  // every team takes one spectrum first and the weights share out the rest: the weighted split alone
+  // rounds a spread team's 31/32 share of n = teams spectra to none (L = 16,384, 9 spectra: team 0
+  // ran two, the ninth team none, and the launch took twice as long)
+  const int64_t one = ta.n >= ta.teams ? 1 : 0, rest = ta.n - one * ta.teams;
+  lo = one * team + (rest * cum(team) + W - 1) / W;             // rounded up: with fewer spectra than
+  hi = one * (team + 1) + (rest * cum(team + 1) + W - 1) / W;   // teams, team 0 takes spectrum 0
 }
 
 template <bool ADS, bool EDGE>

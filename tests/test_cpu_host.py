@@ -367,6 +367,64 @@ def test_team16_xcd_placement_is_a_bijection(teams, TT):
     assert len(seen) == teams * TT
 
 
+TEAM_SWEEP = list(range(1, 41)) + [85, 128, 256]
+
+
+def _team_ranges(n, teams, nloc, xcd=True):
+    from cbam_teams import team_range
+    return [team_range(n, teams, t, nloc, xcd) for t in range(teams)]
+
+
+@pytest.mark.parametrize("xcd", [True, False])
+def test_team_range_partitions_the_batch(xcd):
+    """cbam.hip team_range as restated in tests/cbam_teams.py (what the GPU tests of
+    test_cbam_teams_gpu.py steer by): over teams 1..40, 85, 128, 256, every multiple of 8 local teams
+    and n = 1 .. 3 teams + 2, the teams' ranges are consecutive, do not overlap and cover [0, n); no
+    team is idle while n >= teams (the weighted split alone left the spread ninth team of L = 16,384
+    without a spectrum at n = 9 and gave team 0 two); with n < teams, team 0 takes spectrum 0."""
+    for teams in TEAM_SWEEP:
+        for nloc in range(0, 8 * (teams // 8) + 1, 8):
+            for n in range(1, 3 * teams + 3):
+                rs = _team_ranges(n, teams, nloc, xcd)
+                what = (teams, nloc, n)
+                assert rs[0][0] == 0 and rs[-1][1] == n, what
+                assert all(lo <= hi for lo, hi in rs), what
+                assert all(rs[t][1] == rs[t + 1][0] for t in range(teams - 1)), what
+                if n >= teams:
+                    assert all(lo < hi for lo, hi in rs), what
+                else:
+                    assert rs[0][1] >= 1, what
+
+
+def test_team_rows_name_every_row_once():
+    """cbam_teams.rows_team16 / rows_team: every row has one (team, ordinal), a team's ordinals are
+    0, 1, 2, ... in row order, local teams are the first 8 floor(launched / 8), and a spread team's
+    share never exceeds a local team's by more than the rounding (one spectrum)."""
+    from cbam_teams import launched, rows_team, rows_team16, team16_nloc, team_geo
+    g = team_geo("f16", 1300, 256)
+    assert (g.T, g.TT, g.teams) == (434, 3, 85) and team_geo("fp32", 1300, 256)[:3] == (500, 3, 85)
+    g = team_geo("f16", 16384, 256)
+    assert (g.T, g.TT, g.teams) == (607, 27, 9) and team16_nloc(9, 27) == 8
+    assert team_geo("f16", 256 * 628 + 1, 256).teams == 0 and team_geo("fp32", 256 * 500, 256).teams == 1
+    for teams, TT in [(85, 3), (9, 27), (256, 1), (7, 33), (1, 130)]:
+        for n in [1, 7, 8, 9, teams - 1, teams, teams + 1, 2 * teams + 1, 2 * teams + 3]:
+            if n < 1:
+                continue
+            for rows in (rows_team16(n, teams, TT), rows_team(n, teams)):
+                assert len(rows) == n and all(r is not None for r in rows)
+                seen = {}
+                for r in rows:
+                    assert r.ordinal == seen.get(r.team, 0)
+                    seen[r.team] = r.ordinal + 1
+                assert len(seen) == launched(n, teams)
+            rows = rows_team16(n, teams, TT)
+            nloc = team16_nloc(launched(n, teams), TT)
+            assert nloc % 8 == 0 and all(r.local == (r.team < nloc) for r in rows)
+            count = [sum(1 for r in rows if r.team == t) for t in range(launched(n, teams))]
+            if 0 < nloc < len(count):
+                assert max(count[nloc:]) <= min(count[:nloc]) + 1
+
+
 def test_row_views_and_empty_batches_on_the_host():
     """engine._rows: (N, L) and (N, 1, L) -> contiguous (N, L), N = 0 included (no -1 in the view); and
     the eager (reference) forward of every module on an empty CPU batch returns an empty (0, 1, L)."""

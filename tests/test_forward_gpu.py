@@ -331,7 +331,10 @@ def test_eager_fallback_on_device_matches_engine():
 def test_cbam_team_halo_exchange(arch, L, dtype):
     """CBAM team kernel tiles own T = 512 - 2*6 = 500 positions and refresh their 6-row halos from the
     neighbours' published edge rows at every CBAM: tile-boundary lengths, incl. a last tile that owns
-    fewer positions (1003 = 2*500 + 3) than the 5 edge rows its neighbour reads, against the oracle."""
+    fewer positions (1003 = 2*500 + 3) than the 5 edge rows its neighbour reads, against the oracle.
+    (500 positions hold for team_forward -- fp32, f16f8, bf16x3 -- only: 'f16' runs team16_forward,
+    whose tiles own up to 628 positions spread evenly over L; its own boundaries, 628/629, 1256/1257,
+    ..., are in test_cbam_teams_gpu.py test_team16_tile_boundaries_vs_oracle.)"""
     from oracle.models import forward as oracle_forward
     sd = golden_state_dict(arch, "synth")
     m = _model(arch, "synth", dtype)
