@@ -1781,7 +1781,7 @@ hipError_t launch_cbam_forward(int arch, int dtype, const uint8_t* blob, const f
       e = hipMemsetAsync(sums[pi], 0, (size_t)chunk * 64 * 8, stream);
       if (e == hipSuccess) e = hipMemsetAsync(maxs[pi], 0, (size_t)chunk * 64 * 4, stream);
       if (e != hipSuccess) return e;
-      const int T = WB - 2 * s.halo, tiles = (L + T - 1) / T;
+      const int T = WB - 2 * s.halo, tiles = (int)tiles_of(L, T);
       hipLaunchKernelGGL(k, dim3((unsigned)(nn * tiles)), dim3(THREADS), SEG_LDS_BYTES, stream, blob, xs, ys, L, T, tiles, s);
       e = hipGetLastError();
       if (e != hipSuccess) return e;

@@ -232,7 +232,7 @@ static void launch_median_w(int w, dim3 grid, dim3 block, hipStream_t stream, co
 
 hipError_t launch_fir(const float* x, float* y, int64_t n, int L, const double* taps, int w, const double* edge_taps,
                       hipStream_t stream) {
-  const int tiles = (L + filt::TILE - 1) / filt::TILE;
+  const int tiles = (int)tiles_of(L, filt::TILE);
   return launch_chunks(n, [&](int64_t n0, int64_t nn) {
     hipLaunchKernelGGL(filt::fir_kernel, dim3((unsigned)(nn * tiles)), dim3(filt::THREADS), 0, stream, x + n0 * L,
                        y + n0 * L, L, tiles, taps, w, w > 1 ? edge_taps : nullptr);
@@ -240,7 +240,7 @@ hipError_t launch_fir(const float* x, float* y, int64_t n, int L, const double* 
 }
 
 hipError_t launch_median(const float* x, float* y, int64_t n, int L, int w, hipStream_t stream) {
-  const int tiles = (L + filt::TILE - 1) / filt::TILE;
+  const int tiles = (int)tiles_of(L, filt::TILE);
   return launch_chunks(n, [&](int64_t n0, int64_t nn) {
     const dim3 grid((unsigned)(nn * tiles)), block(filt::THREADS);
     const float* xx = x + n0 * L;

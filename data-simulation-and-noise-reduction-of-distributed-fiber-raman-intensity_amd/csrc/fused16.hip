@@ -147,7 +147,7 @@ hipError_t H16_LAUNCH(int arch, const uint8_t* blob, const float* x, float* y, i
   }
   const hipError_t e = ensure_dynamic_lds((const void*)k, (int)H16_NS::LDS_BYTES, stream_device(stream));
   if (e != hipSuccess) return e;
-  const int H = fused_halo(arch), T = H16_NS::WB - 2 * H, tiles = (L + T - 1) / T;
+  const int H = fused_halo(arch), T = H16_NS::WB - 2 * H, tiles = (int)tiles_of(L, T);
   return launch_chunks(n, [&](int64_t n0, int64_t nn) {
     hipLaunchKernelGGL(k, dim3((unsigned)(nn * tiles)), dim3(H16_NS::THREADS), H16_NS::LDS_BYTES, stream, blob,
                        x + n0 * L, y + n0 * L, L, T, tiles, status);

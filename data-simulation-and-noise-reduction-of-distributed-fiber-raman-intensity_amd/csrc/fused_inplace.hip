@@ -479,7 +479,7 @@ hipError_t launch_fused_inplace_short(const uint8_t* blob, const float* x, float
   const fused_kernel_t k = ip::rrcdnet_short<ip::RRCDNET_F16MIX_TAIL>;
   const hipError_t e = ensure_dynamic_lds((const void*)k, (int)ip::TileGeo<2>::LDS, stream_device(stream));
   if (e != hipSuccess) return e;
-  const int H = fused_halo(RRCDNET), T = ip::TileGeo<2>::WB - 2 * H, tiles = (L + T - 1) / T;
+  const int H = fused_halo(RRCDNET), T = ip::TileGeo<2>::WB - 2 * H, tiles = (int)tiles_of(L, T);
   return launch_chunks(n, [&](int64_t n0, int64_t nn) {
     hipLaunchKernelGGL(k, dim3((unsigned)(nn * tiles)), dim3(THREADS), ip::TileGeo<2>::LDS, stream, blob, x + n0 * L,
                        y + n0 * L, L, T, tiles, status);
@@ -495,7 +495,7 @@ hipError_t launch_fused_inplace_walk(const uint8_t* blob, const float* x, float*
   static_assert(lds_bytes == (uint32_t)ip::HYB_WALK_LDS, "launched with the LDS the kernel and its metric epilogue were compiled for");
   const hipError_t e = ensure_dynamic_lds((const void*)k, (int)lds_bytes, stream_device(stream));
   if (e != hipSuccess) return e;
-  const int H = fused_halo(RRCDNET), T = ip::TileGeo<5>::WB - 2 * H, tiles = (L + T - 1) / T;
+  const int H = fused_halo(RRCDNET), T = ip::TileGeo<5>::WB - 2 * H, tiles = (int)tiles_of(L, T);
   const int ntiles = (int)(((int64_t)L + walk_shift(RRCDNET) + RDN_WALK_ROWS_MIX - 1) / RDN_WALK_ROWS_MIX);
   return launch_chunks(n, [&](int64_t n0, int64_t nn) {
     hipLaunchKernelGGL(k, dim3((unsigned)nn), dim3(THREADS), lds_bytes, stream, blob, x + n0 * L, y + n0 * L, L, T, tiles,
@@ -518,7 +518,7 @@ hipError_t launch_fused_inplace(int arch, int dtype, const uint8_t* blob, const 
   const uint32_t lds = nbk == 4 ? ip::TileGeo<4>::LDS : ip::TileGeo<5>::LDS;
   const hipError_t e = ensure_dynamic_lds((const void*)k, (int)lds, stream_device(stream));
   if (e != hipSuccess) return e;
-  const int H = fused_halo(arch), T = wb - 2 * H, tiles = (L + T - 1) / T;
+  const int H = fused_halo(arch), T = wb - 2 * H, tiles = (int)tiles_of(L, T);
   return launch_chunks(n, [&](int64_t n0, int64_t nn) {
     hipLaunchKernelGGL(k, dim3((unsigned)(nn * tiles)), dim3(THREADS), lds, stream, blob, x + n0 * L,
                        y + n0 * L, L, T, tiles, status);

@@ -130,7 +130,7 @@ __global__ __launch_bounds__(GT) void generate_kernel(uint64_t seed, uint64_t fi
 
   // ---- phase B: signal power of the normalised signal (数据集产生.py:38-43) --------------------
   double ps = 0.0;
-  for (int p = tid; p < L; p += GT) {
+  for (int p = tid; p < L; p += GT) {               // p + GT <= L - 1 + 256 <= INT32_MAX - 1 (rdn_generate's bound)
     const float c = __fdiv_rn(cl[p] - mn, den);
     ps += (double)c * (double)c;
   }
@@ -162,15 +162,15 @@ __global__ __launch_bounds__(GT) void generate_kernel(uint64_t seed, uint64_t fi
   const int ns = s_nspk;
 
   // ---- phase C: normalise, add noise and spikes (数据集产生.py:38-62) --------------------------
-  for (int p0 = 4 * tid; p0 < L; p0 += 4 * GT) {
+  for (int64_t p0 = 4 * tid; p0 < L; p0 += 4 * GT) {   // 64 bits: p0 + 4 GT passes 2^31 for L > 2^31 - 4 GT
     const U4 r = philox((uint32_t)(p0 >> 2), TAG_NOISE, ilo, ihi, seed);
     float z[4];
     box_muller(r.x, r.y, z[0], z[1]);
     box_muller(r.z, r.w, z[2], z[3]);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int p = p0 + i;
-      if (p >= L) break;
+      if (p0 + i >= L) break;
+      const int p = (int)(p0 + i);
       const float c = __fdiv_rn(cl[p] - mn, den);
       float v = c + sigma * z[i];
       for (int s = 0; s < ns; ++s) {

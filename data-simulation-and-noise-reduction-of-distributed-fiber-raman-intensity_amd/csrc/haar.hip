@@ -225,7 +225,7 @@ __global__ __launch_bounds__(THREADS) void shrink_kernel(const float* __restrict
 
 hipError_t launch_haar_shrink(const float* x, float* y, double* med, int64_t n, int L, int levels,
                               const haar::Factors& k, int mode, hipStream_t stream) {
-  const int tiles = (L + haar::TILE - 1) / haar::TILE;
+  const int tiles = (int)tiles_of(L, haar::TILE);
   const size_t lds = (size_t)haar::shrink_lds_bytes(levels);
   return launch_chunks(n, [&](int64_t n0, int64_t nn) {
     const dim3 block(haar::THREADS), rows((unsigned)nn), grid((unsigned)(nn * tiles));

@@ -17,7 +17,8 @@
 // And the pure host helpers of the launch path, which no device test can reach: the once-per-(kernel,
 // device) bookkeeping of the LDS opt-in with a counting fake setter (host_util.hpp once_per: repeats,
 // device bounds, a failing setter, 8 racing threads, a full table), the chunk walk (for_chunks,
-// tiles_chunk: 2^33 workgroups in 5 launches), overlaps(), and the forward's geometry choice
+// tiles_chunk: 2^33 workgroups in 5 launches; tiles_of and the chunk of every tile size up to rows of
+// 2^31 - 1 samples; the refusal of a chunk below 1), overlaps(), and the forward's geometry choice
 // (geometry.hpp forward_geometry) against values derived by hand from its formulas.
 #include <cmath>
 #include <cstdint>
@@ -95,12 +96,12 @@ static void check_chunks() {
   const auto walk = [](int64_t n, int64_t chunk) {
     int64_t next = 0, calls = 0;
     bool good = true;
-    rdn::for_chunks(n, chunk, [&](int64_t n0, int64_t nn) {
+    const hipError_t e = rdn::for_chunks(n, chunk, [&](int64_t n0, int64_t nn) {
       good = good && n0 == next && nn >= 1 && nn <= chunk;
       next = n0 + nn;
       ++calls;
     });
-    return good && next == (n > 0 ? n : 0) ? calls : (int64_t)-1;
+    return e == hipSuccess && good && next == (n > 0 ? n : 0) ? calls : (int64_t)-1;
   };
   EXPECT(walk(0, 7) == 0);
   EXPECT(walk(7, 7) == 1);
@@ -109,6 +110,35 @@ static void check_chunks() {
   EXPECT(walk((int64_t)1 << 33, 0x7fffffff) == 5);         // 4 (2^31 - 1) = 2^33 - 4: a fifth launch of 4
   EXPECT(rdn::tiles_chunk(18) * 18 <= 0x7fffffff && (rdn::tiles_chunk(18) + 1) * 18 > 0x7fffffff);
   EXPECT(rdn::tiles_chunk(1) == 0x7fffffff);
+
+  // a chunk below 1 is refused without a call (forwards it would never end, backwards it would leave the buffer)
+  for (int64_t chunk : {(int64_t)0, (int64_t)-1, (int64_t)-2048}) {
+    int64_t calls = 0;
+    EXPECT(rdn::for_chunks(1, chunk, [&](int64_t, int64_t) { ++calls; }) == hipErrorInvalidValue && calls == 0);
+    EXPECT(rdn::for_chunks(0, chunk, [&](int64_t, int64_t) { ++calls; }) == hipErrorInvalidValue && calls == 0);
+    EXPECT(rdn::launch_chunks(1, [&](int64_t, int64_t) { ++calls; }, chunk) == hipErrorInvalidValue && calls == 0);
+  }
+  EXPECT(rdn::for_chunks(3, 2, [](int64_t, int64_t) {}) == hipSuccess);
+  EXPECT(rdn::tiles_chunk(0) == 0 && rdn::tiles_chunk(-1048575) == 0);
+
+  // Every tile size a launcher uses (the filters' 2048, Haar's 512, the positions a forward's tile owns: 198 to
+  // 628) at every admitted row length where the count could slip: the tile count is the exact ceiling and a
+  // positive int, its chunk is at least one spectrum and fills grid.x at most, and the walk covers the batch.
+  const int64_t top = (int64_t)1 << 31;
+  for (int64_t T : {(int64_t)2048, (int64_t)512, (int64_t)198, (int64_t)500, (int64_t)582, (int64_t)600, (int64_t)628}) {
+    for (int64_t L : {(int64_t)1, T - 1, T, T + 1, top - T, top - T + 1, top - 1}) {
+      const int64_t tiles = rdn::tiles_of(L, T);
+      // the ceiling by its definition, without the sum that wraps: (tiles - 1) T < L <= tiles T
+      EXPECT(tiles >= 1 && tiles <= 0x7fffffff && (tiles - 1) * T < L && L <= tiles * T);
+      EXPECT((int)tiles == tiles);
+      const int64_t chunk = rdn::tiles_chunk(tiles);
+      EXPECT(chunk >= 1 && chunk * tiles <= 0x7fffffff && (chunk + 1) * tiles > 0x7fffffff);
+      if (chunk < 1) continue;                 // reported above
+      EXPECT(walk(1, chunk) == 1);
+      const int64_t n = (int64_t)1 << 33;      // the smallest chunk here is 198 spectra: 4.3e7 calls
+      EXPECT(walk(n, chunk) == (n + chunk - 1) / chunk);
+    }
+  }
 }
 
 static void check_overlaps() {

@@ -115,22 +115,31 @@ inline hipError_t with_clean(const void* clean, bool clean_f64, F f) {
   return clean_f64 ? f((const double*)clean) : f((const float*)clean);
 }
 
-// [0, n) in consecutive pieces of at most `chunk`: f(n0, nn) for the nn that start at n0.
+// [0, n) in consecutive pieces of at most `chunk`: f(n0, nn) for the nn that start at n0.  A chunk below 1
+// is refused without a call of f (hipErrorInvalidValue): the walk would not advance, or would run backwards.
 template <class F>
-inline void for_chunks(int64_t n, int64_t chunk, F f) {
+inline hipError_t for_chunks(int64_t n, int64_t chunk, F f) {
+  if (chunk < 1) return hipErrorInvalidValue;
   for (int64_t n0 = 0; n0 < n; n0 += chunk) f(n0, n - n0 < chunk ? n - n0 : chunk);
+  return hipSuccess;
 }
 
+// Workgroups per spectrum of a kernel whose tiles own T positions each: the exact ceil(L / T), computed in
+// 64 bits (in `int`, L + T - 1 wraps for the longest admitted rows, L > 2^31 - T).  For 1 <= L < 2^31 and
+// T >= 1 the result is positive and fits `int`.
+inline int64_t tiles_of(int64_t L, int64_t T) { return L / T + (L % T != 0); }
+
 // spectra of one launch of a kernel that runs `tiles` workgroups per spectrum: their tiles fill grid.x
-inline int64_t tiles_chunk(int64_t tiles) { return 0x7fffffff / tiles; }
+// (0, which launch_chunks refuses, for a tile count that is not positive)
+inline int64_t tiles_chunk(int64_t tiles) { return tiles < 1 ? 0 : 0x7fffffff / tiles; }
 
 // Walks a batch of n workgroups (one per spectrum) in launches of at most 2^31 - 1, the grid's limit in
 // x: launch(n0, nn) enqueues the nn of them that start at n0.  (`chunk`: fewer spectra per launch, for a
 // kernel that runs several workgroups per spectrum: tiles_chunk.)
 template <class Launch>
 inline hipError_t launch_chunks(int64_t n, Launch launch, int64_t chunk = 0x7fffffff) {
-  for_chunks(n, chunk, launch);
-  return hipGetLastError();
+  const hipError_t e = for_chunks(n, chunk, launch);
+  return e != hipSuccess ? e : hipGetLastError();
 }
 
 // the byte ranges [a, a + abytes) and [b, b + bbytes) share a byte (an empty range shares none)

@@ -21,7 +21,7 @@ __global__ __launch_bounds__(MET_THREADS) void metrics_kernel(const float* __res
   __shared__ double red[RED_DOUBLES];
   const int64_t n = __builtin_amdgcn_workgroup_id_x();
   const float* yy = y + (size_t)n * L;
-  spectrum_metrics([&](int p) { return yy[p]; }, clean + (size_t)n * L, L, n, red, mo);
+  spectrum_metrics<int64_t>([&](int64_t p) { return yy[p]; }, clean + (size_t)n * L, L, n, red, mo);
 }
 
 }  // namespace met

@@ -125,8 +125,10 @@ __device__ __forceinline__ void acc_add(long long* acc, int q, double v) {
 
 // The four metrics of spectrum n (denoised values through yv(p), clean cc[0..L)), every thread of the
 // MET_THREADS-thread workgroup taking part; red: RED_DOUBLES doubles of LDS.  Results: per[n],
-// sums, acc of mo (each optional).
-template <typename TC, class YV>
+// sums, acc of mo (each optional).  IX: the type of a position.  `int` serves the walk epilogue, which the host
+// fuses for L < 2^29 only; a caller that takes every admitted L < 2^31 passes int64_t, since p + MET_THREADS
+// and i + 7 pass 2^31 in `int` for L > 2^31 - MET_THREADS.
+template <typename IX = int, typename TC, class YV>
 __device__ __forceinline__ void spectrum_metrics(YV yv, const TC* __restrict__ cc, int L, int64_t n, double* red,
                                                  const MetricOut& mo) {
   const int tid = __builtin_amdgcn_workitem_id_x();
@@ -134,7 +136,7 @@ __device__ __forceinline__ void spectrum_metrics(YV yv, const TC* __restrict__ c
 
   double se = 0.0, sm = 0.0, ymax = -INFINITY, ymin = INFINITY, cmax = -INFINITY, cmin = INFINITY;
   bool nan_y = false, nan_c = false;
-  for (int p = tid; p < L; p += MET_THREADS) {
+  for (IX p = tid; p < L; p += MET_THREADS) {
     const float af = yv(p);
     const TC cv = cc[p];
     nan_y |= nan_bits(af);
@@ -159,7 +161,7 @@ __device__ __forceinline__ void spectrum_metrics(YV yv, const TC* __restrict__ c
   const double C1 = (0.01 * R) * (0.01 * R), C2 = (0.03 * R) * (0.03 * R);
   const double cov = 7.0 / 6.0;
   double ss = 0.0;
-  for (int i = tid; i + 7 <= L; i += MET_THREADS) {
+  for (IX i = tid; i + 7 <= L; i += MET_THREADS) {
     double sx = 0, sy = 0, sxx = 0, syy = 0, sxy = 0;
 #pragma unroll
     for (int k = 0; k < 7; ++k) {

@@ -3,6 +3,12 @@
 All compute runs in libraman_mi355x.so on the caller's current HIP stream; these functions only
 check shapes/devices, allocate outputs through the PyTorch caching allocator and pass raw
 pointers.  Nothing here has a CPU or PyTorch-op fallback.
+
+Every call enqueues on ``torch.cuda.current_stream(x.device)`` -- the stream of the device that holds the
+tensors, whichever device is current -- and returns without waiting.  The calls that wait on the host are the
+ones that read a status word back: ``check=True`` of forward() / forward_metrics(), Workspace.check() and
+Workspace.read_status().  A filter given host taps copies them to the device first, which also waits.
+(tests/test_launch_contract_gpu.py)
 """
 import ctypes
 import math

@@ -6,6 +6,11 @@
  * a message for rdn_last_error() (thread-local).  No exception crosses the ABI.  All device
  * buffers are owned by the caller (e.g. the PyTorch caching allocator); the library keeps no
  * device state of its own, enqueues on the caller's stream and never synchronises it.
+ * Every kernel and memset of a call goes to the stream it was given, on the device that owns that
+ * stream (which need not be the current device), and the call returns without waiting for them.  The
+ * two exceptions read status words back and so wait for the stream: rdn_forward_status and
+ * rdn_forward_status_ex.  Rows of every admitted length (L < 2^31) get a tile count computed in 64
+ * bits, and no launcher walks a batch in chunks below one spectrum.
  *
  * Reference interfaces these entry points replace (paths relative to the reference repo):
  *   rdn_param_names / rdn_packed_size / rdn_pack
